@@ -18,6 +18,11 @@ to the global batch. ``--engine collab`` times the collaborative optimizer's own
 Data: synthetic LAION-shaped pairs (256 caption ids padded with 1, 1024 VQGAN codes), random-init
 weights. Rank 0 prints ONE JSON line.
 
+A plain run sets up, warms up, times ``--steps`` steps and prints that line. ``--dump-outputs DIR`` also writes
+what the last timed step produced (``loss.npy``, ``params.npy``, ``grads.npy``; the inputs and the initial weights
+are seeded, so two builds can be compared output for output). ``--full`` adds the measurements that need runs of
+their own (world > 1: the gradient all-reduce alone, ``grad_allreduce.standalone_ms`` / ``busbw_GBps`` / ``buckets``).
+
 CPU rehearsal: ``BENCH_BACKEND=gloo python bench.py --gpus 2 --model tiny --batch 2`` runs the same
 path with gloo on CPU when no GPU is visible (tests/test_bench_cpu.py).
 """
@@ -93,6 +98,13 @@ def parse():
                          "(false) or keep as many blocks as the free HBM holds (auto)")
     ap.add_argument("--tunable", default="off", choices=["auto", "use", "tune", "off"],
                     help="hipBLASLt solution selection for the library GEMMs (dalle_amd/utils/tuning.py)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step produced as DIR/<name>.npy (float32): "
+                         "loss, and a fixed seeded sample of the updated parameters and of the gradients it applied")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements that take runs of their own (world > 1: the gradient all-reduce "
+                         "alone, whole and per bucket, for its standalone time and bus bandwidth); a plain run only "
+                         "times the steps")
     return ap.parse_args()
 
 
@@ -174,6 +186,26 @@ def _param_groups(model):
 def _lamb(groups, bits, arena=None):
     return LAMB8bit(groups, lr=0.0025, betas=(0.9, 0.96), eps=1e-6, weight_decay=0.045, clamp_value=10000.0,
                     max_grad_norm=4.0, reuse_grad_buffers=True, optim_bits=bits, arena=arena)
+
+
+DUMP_SAMPLE = 1 << 22  # elements kept of each flat buffer: 16 MB of float32 per file
+
+
+def dump_outputs(path, loss, arena) -> None:
+    """What the last timed step handed back, as float32 ``.npy`` files: its loss, the parameters after its
+    optimizer update and the gradient arena as that step left it (--engine step: the averaged gradients it
+    applied). The flat buffers are sampled at fixed positions (seeded, sorted, the same for every run of the
+    same model), so two builds compare element for element."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    if arena.numel > DUMP_SAMPLE:
+        idx = torch.randint(arena.numel, (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(4321)).sort().values
+    else:
+        idx = torch.arange(arena.numel)
+    np.save(os.path.join(path, "loss.npy"), loss.detach().float().cpu().reshape(1).numpy())
+    for name, buf in (("params", arena.data), ("grads", arena.grad)):
+        np.save(os.path.join(path, f"{name}.npy"), buf.detach()[idx.to(buf.device)].float().cpu().numpy())
 
 
 def run_rank(args) -> None:
@@ -335,6 +367,8 @@ def run_rank(args) -> None:
     elapsed = time.perf_counter() - t0
     if args.engine == "collab":
         copt.apply_pending()
+    if args.dump_outputs and rank == 0:  # every rank holds the same parameters and averaged gradients
+        dump_outputs(args.dump_outputs, loss, arena)
     per_rank = [elapsed]
     names = [torch.cuda.get_device_name(device) if use_cuda else "cpu"]
     if world > 1:
@@ -352,27 +386,30 @@ def run_rank(args) -> None:
         exposed = comm.exposed_ms() / args.steps if use_cuda else None
         step_bytes = comm.bytes_reduced / args.steps
         overlapped = round(comm.last_early_elems / max(1, arena.numel), 3)
-        # the same all-reduce (same buckets) alone, to price the bytes: bus bandwidth as nccl-tests reports it
-        g = arena.grad
-        saved = g.clone()
-        sync()
-        dist.barrier()
-        ta = time.perf_counter()
-        for _ in range(3):
-            comm.all_reduce()
-        sync()
-        t_ar = (time.perf_counter() - ta) / 3
-        g.copy_(saved)
-        del saved
-        t_all = [None] * world
-        dist.all_gather_object(t_all, t_ar)
-        t_ar = max(t_all)
-        comm_stats = {"algo": args.allreduce_algo, "buckets": comm.bucket_busbw(),
+        t_ar = None
+        if args.full:
+            # the same all-reduce (same buckets) alone, to price the bytes: bus bandwidth as nccl-tests reports it
+            g = arena.grad
+            saved = g.clone()
+            sync()
+            dist.barrier()
+            ta = time.perf_counter()
+            for _ in range(3):
+                comm.all_reduce()
+            sync()
+            t_ar = (time.perf_counter() - ta) / 3
+            g.copy_(saved)
+            del saved
+            t_all = [None] * world
+            dist.all_gather_object(t_all, t_ar)
+            t_ar = max(t_all)
+        comm_stats = {"algo": args.allreduce_algo, "buckets": comm.bucket_busbw() if args.full else None,
                       "selected": {"algo": args.allreduce_algo, "bucket_mb": round(comm.bucket_elems * 4 / 2 ** 20, 1),
                                    "tuned": ar_tuning is not None},
                       "tuning": ar_tuning,
-                      "bytes_per_step": int(step_bytes), "standalone_ms": round(t_ar * 1e3, 3),
-                      "busbw_GBps": round(2 * (world - 1) / world * step_bytes / t_ar / 1e9, 1),
+                      "bytes_per_step": int(step_bytes),
+                      "standalone_ms": None if t_ar is None else round(t_ar * 1e3, 3),
+                      "busbw_GBps": None if t_ar is None else round(2 * (world - 1) / world * step_bytes / t_ar / 1e9, 1),
                       "exposed_ms_per_step": None if exposed is None else round(exposed, 3),
                       "overlapped_frac": overlapped}
     peaks = [peak_gb]

@@ -28,7 +28,8 @@ def _run(tmp_path, *extra):
 
 @pytest.mark.parametrize("engine", ["step", "collab"])
 def test_bench_spawns_n_ranks(tmp_path, engine):
-    res, p0, p1 = _run(tmp_path, "--engine", engine)
+    # --full: the standalone all-reduce (standalone_ms, busbw_GBps below) is a run of its own
+    res, p0, p1 = _run(tmp_path, "--engine", engine, "--full")
     assert res["n_gpus"] == 2 and res["config"]["parallelism"] == "dp2" and res["config"]["global_batch"] == 4
     assert len(res["per_rank_ms_per_step"]) == 2 and res["value"] > 0
     assert len(res["per_rank_peak_mem_gb"]) == 2
@@ -66,7 +67,7 @@ def test_bench_allreduce_algorithms(tmp_path, n):
         env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
         env.update(BENCH_BACKEND="gloo", BENCH_DUMP_PARAMS=str(d / "params"), HIP_VISIBLE_DEVICES="")
         out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "2", "--warmup", "1",
-                              "--model", "tiny", "--batch", "2", "--allreduce-algo", algo], env=env, cwd=str(d),
+                              "--model", "tiny", "--batch", "2", "--allreduce-algo", algo, "--full"], env=env, cwd=str(d),
                              capture_output=True, text=True, timeout=600)
         assert out.returncode == 0, out.stderr[-3000:]
         res = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][0])
@@ -122,7 +123,37 @@ def test_bench_bf16_wire(tmp_path):
     ar = res["grad_allreduce"]
     assert res["config"]["grad_allreduce_dtype"] == "bf16" and ar["selected"]["bucket_mb"] == 1.0
     assert not ar["selected"]["tuned"] and ar["tuning"] is None
+    # a plain run: no all-reduce runs of their own
+    assert ar["standalone_ms"] is None and ar["busbw_GBps"] is None and ar["buckets"] is None
     assert torch.equal(p0, p1)
+
+
+def test_bench_dump_outputs_repeatable(tmp_path):
+    """--dump-outputs: the last timed step's loss, parameters and gradients as float32 .npy files; the inputs and
+    the initial weights are seeded, so a second run with the same arguments writes the same arrays."""
+    import numpy as np
+
+    def run(name, steps):
+        env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+        env.update(BENCH_BACKEND="gloo", HIP_VISIBLE_DEVICES="")
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps),
+                              "--warmup", "1", "--model", "tiny", "--batch", "2", "--dump-outputs", str(tmp_path / name)],
+                             env=env, cwd=str(tmp_path), capture_output=True, text=True, timeout=300)
+        assert out.returncode == 0, out.stderr[-3000:]
+        res = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][0])
+        assert res["steps"] == steps and res["ms_per_step"] > 0
+        files = sorted(os.listdir(tmp_path / name))
+        assert files == ["grads.npy", "loss.npy", "params.npy"]
+        arrays = {f[:-4]: np.load(tmp_path / name / f) for f in files}
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64 * 2 ** 20
+        assert abs(float(arrays["loss"][0]) - res["loss"]) <= 1e-4
+        assert arrays["params"].shape == arrays["grads"].shape and np.abs(arrays["grads"]).sum() > 0
+        return arrays
+
+    a, b = run("a", 2), run("b", 2)
+    for k in a:
+        np.testing.assert_allclose(a[k], b[k], rtol=1e-6, atol=1e-7)
 
 
 def test_bench_fixed_bucket_with_auto_algorithm(tmp_path):
