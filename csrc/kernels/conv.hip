@@ -10,8 +10,8 @@
 //   way to LDS (per-channel scale / shift of this image from an LDS table), so the normalised
 //   activation never exists in memory. The 2x nearest upsampling in front of the Upsample conv is
 //   folded into the same gather (source pixel = shifted pixel / 2). Register-staged double buffer
-//   (next K-step's global loads in flight during the MFMAs), XOR-swizzled LDS rows, bf16 epilogue
-//   through LDS with the bias and the ResNet residual added on the way out.
+//   (next K-step's global loads in flight during the MFMAs), XOR-swizzled LDS rows, fp32 epilogue
+//   through LDS with the bias and the ResNet residual added on the way out (one rounding to bf16).
 // * gn_stats: GroupNorm (32 groups) mean / rstd per (image, group): per-workgroup partial sums over a
 //   pixel range, reduced in a fixed order in double (deterministic).
 // * gn_apply: GroupNorm without activation into bf16 (the attention block's input).
@@ -136,9 +136,14 @@ __global__ __launch_bounds__(CV_THREADS, 2) void conv3x3_kernel(ConvArgs a) {
     __syncthreads();
   }
 
-  // epilogue: the 128 x 128 tile as bf16 through LDS (rows of 256 B, 16-byte chunks swizzled by row),
-  // then 16-byte stores of whole channel runs with bias + residual
-  __bf16* ep = smem;
+  // epilogue: the 128 x 128 tile as FP32 through LDS (rows of 512 B = the whole 64 KiB of the operand buffers;
+  // 16-byte chunks XOR-swizzled by the row's quad and parity (ep_sw), so the 2 x 16 accumulator elements of a
+  // 32-lane write group fall on 32 banks and the chunks 2 ch (+ 1) that a 16-lane read group takes from an even
+  // and an odd row on 64), then bias + residual in fp32 and ONE rounding to bf16, 16-byte stores of whole
+  // channel runs. (Staging the tile as bf16 rounded the convolution before bias / residual were added and the
+  // sum a second time.)
+  float* ep = reinterpret_cast<float*>(smem);
+  auto ep_sw = [](int row) { return (((row >> 2) & 3) << 2) ^ (row & 1); };
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const int c = wn * 64 + j * 16 + fr;
@@ -147,16 +152,17 @@ __global__ __launch_bounds__(CV_THREADS, 2) void conv3x3_kernel(ConvArgs a) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int row = wm * 64 + i * 16 + fq * 4 + r;
-        ep[row * 128 + ((((c >> 3) ^ (row & 15)) << 3) | (c & 7))] = (__bf16)acc[i][j][r];
+        ep[row * 128 + ((((c >> 2) ^ ep_sw(row)) << 2) | (c & 3))] = acc[i][j][r];
       }
   }
   __syncthreads();
 #pragma unroll
   for (int it = 0; it < 8; ++it) {
-    const int idx = it * CV_THREADS + tid;  // 128 rows x 16 chunks
+    const int idx = it * CV_THREADS + tid;  // 128 rows x 16 runs of 8 channels
     const int row = idx >> 4, ch = idx & 15;
-    float f[8];
-    unpack8(*reinterpret_cast<const s16x8*>(ep + row * 128 + ((ch ^ (row & 15)) << 3)), f);
+    const f32x4 v0 = *reinterpret_cast<const f32x4*>(ep + row * 128 + (((2 * ch) ^ ep_sw(row)) << 2));
+    const f32x4 v1 = *reinterpret_cast<const f32x4*>(ep + row * 128 + (((2 * ch + 1) ^ ep_sw(row)) << 2));
+    float f[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
     const int co = n0 + ch * 8;
     if (a.bias != nullptr) {
       const f32x4 b0 = *reinterpret_cast<const f32x4*>(a.bias + co), b1 = *reinterpret_cast<const f32x4*>(a.bias + co + 4);

@@ -233,11 +233,11 @@ class VQGanVAE(nn.Module):
 
     @torch.no_grad()
     def decode(self, img_seq: torch.Tensor) -> torch.Tensor:
-        if img_seq.is_cuda and self.use_hip_decoder():
+        b, n = img_seq.shape
+        side = int(round(n ** 0.5))
+        if img_seq.is_cuda and self.use_hip_decoder(side, side):
             # K20 on the hand-written HIP kernels (models/vqgan_hip.py): NHWC bf16 from the codebook gather on
             hip = self._hip_decoder
-            b, n = img_seq.shape
-            side = int(round(n ** 0.5))
             cb = self._codebook_bf16()
             z = F.embedding(img_seq.long(), cb).view(b, side, side, cb.shape[1])
             return hip(z)
@@ -247,13 +247,17 @@ class VQGanVAE(nn.Module):
 
     hip_decoder = True  # False: the PyTorch / MIOpen decoder (numerics A/B in tests/test_vqgan_gpu.py)
 
-    def use_hip_decoder(self) -> bool:
-        """True when the decoder runs on the HIP kernels (MI355X, supported channel layout, ``hip_decoder``)."""
+    def use_hip_decoder(self, h: Optional[int] = None, w: Optional[int] = None) -> bool:
+        """True when the decoder runs on the HIP kernels (MI355X, supported channel layout, ``hip_decoder``); with
+        ``h, w`` also whether a code grid of that size does: one the 3x3 conv kernel cannot tile (8 x 8, 24 x 24)
+        goes to the PyTorch decoder for that call, and the cached ``HipDecoder`` stays for the next."""
         if not self.hip_decoder:
             return False
-        if getattr(self, "_hip_decoder", None) is None:
-            from .vqgan_hip import HipDecoder, supported
+        from .vqgan_hip import HipDecoder, grid_supported, supported
 
+        if h is not None and not grid_supported(h, w if w is not None else h):
+            return False
+        if getattr(self, "_hip_decoder", None) is None:
             if not supported(self.decoder):
                 return False
             self._hip_decoder = HipDecoder(self.post_quant_conv, self.decoder)

@@ -135,9 +135,18 @@ class HipDecoder:
         return self.C.conv_out(x, wout, bout, mean, rstd, gamma, beta)
 
 
+def grid_supported(h: int, w: int) -> bool:
+    """``conv3x3`` tiles 128 pixels of one image: every 3x3 conv's input pixel count must be a multiple of 128.
+    The levels only upsample (x4 pixels each), so the latent grid decides it."""
+    return h > 0 and w > 0 and (h * w) % 128 == 0
+
+
 def supported(decoder: Decoder) -> bool:
     """The HIP path needs channel counts the kernels tile (multiples of 128 for the 3x3 convs, <= 128
-    channels into the RGB conv) and 32-group GroupNorms."""
+    channels into the RGB conv) and 32-group GroupNorms. The code grid of a call is checked per call
+    (:func:`grid_supported`)."""
+    if any(m.num_groups != 32 for m in decoder.modules() if isinstance(m, torch.nn.GroupNorm)):
+        return False
     convs: List[torch.nn.Conv2d] = [m for m in decoder.modules() if isinstance(m, torch.nn.Conv2d) and m.kernel_size == (3, 3)]
     for m in convs:
         if m is decoder.conv_out:

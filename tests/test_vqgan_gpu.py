@@ -67,6 +67,54 @@ def test_conv_out_kernel_vs_torch(cuda, n, h, w, cin):
     assert (img - ref).abs().max().item() < 2e-2, (n, h, w, cin, (img - ref).abs().max().item())
 
 
+DDCONFIG = dict(ch=128, out_ch=3, ch_mult=(1, 2, 4), num_res_blocks=1, attn_resolutions=(16,), resolution=64,
+                z_channels=256)
+
+
+def test_hip_decoder_gather_form_matches_torch(cuda, monkeypatch):
+    """The fused-gather GroupNorm form of conv3x3 (still selectable, no longer the default) through the whole
+    decoder: same bounds against the torch decoder as the pre-pass form, and the two HIP forms are closer to each
+    other than either is to torch."""
+    from dalle_amd.models import vqgan_hip
+
+    torch.manual_seed(0)
+    vae = VQGanVAE(n_embed=512, embed_dim=256, ddconfig=DDCONFIG).to(cuda).eval()
+    codes = torch.randint(0, 512, (3, 16 * 16), device=cuda)
+    assert vae.use_hip_decoder()
+    assert vqgan_hip._GN_PREPASS_MIN_HW == 0
+    pre = vae.decode(codes)
+    monkeypatch.setattr(vqgan_hip, "_GN_PREPASS_MIN_HW", 10 ** 9)
+    img = vae.decode(codes)
+    monkeypatch.setattr(vae, "hip_decoder", False)
+    ref = vae.decode(codes)
+    assert img.shape == ref.shape == (3, 3, 64, 64)
+    assert img.dtype == torch.float32 and img.min() >= 0 and img.max() <= 1
+    err = (img - ref).abs()
+    assert err.mean().item() < 1e-2 and _rel(img - 0.5, ref - 0.5) < 5e-2, (err.mean().item(), err.max().item())
+    forms = (img - pre).abs().mean().item()
+    assert not torch.equal(img, pre)  # the other form did run
+    assert forms < min(err.mean().item(), (pre - ref).abs().mean().item()), (forms, err.mean().item())
+
+
+@pytest.mark.parametrize("b,side", [(2, 8), (1, 24)])
+def test_decode_falls_back_on_untiled_grid(cuda, monkeypatch, b, side):
+    """conv3x3 tiles 128 pixels of one image: an 8 x 8 or 24 x 24 code grid (64 / 576 pixels) is decoded by the
+    PyTorch decoder for that call, as an unsupported channel layout is, and the HIP decoder stays cached."""
+    torch.manual_seed(0)
+    vae = VQGanVAE(n_embed=512, embed_dim=256, ddconfig=DDCONFIG).to(cuda).eval()
+    codes = torch.randint(0, 512, (b, side * side), device=cuda)
+    assert vae.use_hip_decoder() and not vae.use_hip_decoder(side, side) and vae.use_hip_decoder(16, 16)
+    hip = vae._hip_decoder
+    img = vae.decode(codes)
+    assert vae._hip_decoder is hip
+    monkeypatch.setattr(vae, "hip_decoder", False)
+    ref = vae.decode(codes)
+    assert img.shape == ref.shape == (b, 3, 4 * side, 4 * side)
+    # the same fp32 PyTorch path twice (1e-5 leaves room for a convolution library choosing another algorithm on
+    # the second call; the bf16 HIP path is ~1e-3 away)
+    assert (img - ref).abs().max().item() <= 1e-5
+
+
 def test_hip_decoder_matches_torch(cuda, monkeypatch):
     torch.manual_seed(0)
     ddconfig = dict(ch=128, out_ch=3, ch_mult=(1, 2, 4), num_res_blocks=1, attn_resolutions=(16,), resolution=64,
