@@ -52,6 +52,8 @@ bool xent_colsum(void*, const int64_t*, float*, float*, long, int, float, hipStr
 void transpose_cast_bf16(const float* w, void* wt, int R, int C, hipStream_t st);
 void transpose_bf16(const void* x, void* xt, int R, int C, hipStream_t st);
 bool conv3x3(const ConvArgs&, hipStream_t);
+bool conv_in_rgb(const float*, const void*, const float*, void*, int, int, int, int, hipStream_t);
+bool linear_argmax(const void*, const void*, const float*, int64_t*, long, int, int, hipStream_t);
 bool gn_stats(const void*, float*, float*, float*, int, int, int, float, hipStream_t);
 size_t gn_part_floats(int);
 void gn_apply(const void*, const float*, const float*, const float*, const float*, void*, int, int, int, hipStream_t, int);
@@ -1013,14 +1015,20 @@ static const float* opt_f32(const c10::optional<Tensor>& t, long n, const char* 
   return t->data_ptr<float>();
 }
 
-// y (N, H, W, Cout) = conv3x3(silu(GN(x)) or x, upsampled 2x if ups) + bias (+ res)
+// y (N, H, W, Cout) = conv3x3(silu(GN(x)) or x, upsampled 2x if ups) + bias (+ res); down: the encoder's Downsample
+// (zero pad right / bottom, stride 2): y (N, H / 2, W / 2, Cout), no ups / GroupNorm / residual
 Tensor conv3x3(Tensor x, Tensor w, c10::optional<Tensor> bias, c10::optional<Tensor> res, c10::optional<Tensor> mean,
-               c10::optional<Tensor> rstd, c10::optional<Tensor> gamma, c10::optional<Tensor> beta, bool ups) {
+               c10::optional<Tensor> rstd, c10::optional<Tensor> gamma, c10::optional<Tensor> beta, bool ups, bool down) {
   CHECK_IN(x, torch::kBFloat16); CHECK_IN(w, torch::kBFloat16);
   TORCH_CHECK(x.dim() == 4 && w.dim() == 2, "conv3x3: x (N, H, W, Cin) NHWC, w (Cout, 9 * Cin)");
   const int N = x.size(0), Hs = x.size(1), Ws = x.size(2), Cin = x.size(3), Cout = w.size(0);
   TORCH_CHECK(w.size(1) == 9 * Cin, "conv3x3: weight / input channels mismatch");
-  const int H = ups ? 2 * Hs : Hs, W = ups ? 2 * Ws : Ws;
+  const char* unsupported = "conv3x3: unsupported shape (Cin % 64, Cout % 128, H*W % 128, Cin <= 1024; down: even H, W, "
+                            "no ups / GroupNorm / residual)";
+  TORCH_CHECK(!down || (!ups && !mean.has_value() && !res.has_value() && Hs % 2 == 0 && Ws % 2 == 0 && Hs > 0 && Ws > 0),
+              unsupported);
+  const int H = down ? Hs / 2 : ups ? 2 * Hs : Hs, W = down ? Ws / 2 : ups ? 2 * Ws : Ws;
+  TORCH_CHECK(!down || ((long)H * W) % 128 == 0, unsupported);
   auto y = torch::empty({N, H, W, Cout}, x.options());
   dalle::ConvArgs a{};
   a.x = x.data_ptr();
@@ -1040,9 +1048,34 @@ Tensor conv3x3(Tensor x, Tensor w, c10::optional<Tensor> bias, c10::optional<Ten
     TORCH_CHECK(a.rstd && a.gamma && a.beta, "conv3x3: GroupNorm needs mean, rstd, gamma, beta");
   }
   a.y = y.data_ptr();
-  a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.ups = ups ? 1 : 0;
-  TORCH_CHECK(dalle::conv3x3(a, cur_stream()), "conv3x3: unsupported shape (Cin % 64, Cout % 128, H*W % 128, Cin <= 1024)");
+  a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.ups = ups ? 1 : 0; a.down = down ? 1 : 0;
+  TORCH_CHECK(dalle::conv3x3(a, cur_stream()), unsupported);
   return y;
+}
+
+// Encoder input conv: images (N, 3, H, W) fp32 in [0, 1] -> conv3x3(bf16(2 x - 1)) + bias, (N, H, W, Cout) bf16 NHWC
+Tensor conv_in_rgb(Tensor images, Tensor w, Tensor bias) {
+  CHECK_IN(images, torch::kFloat32); CHECK_IN(w, torch::kBFloat16); CHECK_IN(bias, torch::kFloat32);
+  TORCH_CHECK(images.dim() == 4 && images.size(1) == 3 && w.dim() == 2 && w.size(1) == 27 && bias.numel() == w.size(0),
+              "conv_in_rgb: images (N, 3, H, W), w (Cout, 27), bias (Cout)");
+  const int N = images.size(0), H = images.size(2), W = images.size(3), Cout = w.size(0);
+  auto y = torch::empty({N, H, W, Cout}, images.options().dtype(torch::kBFloat16));
+  TORCH_CHECK(N > 0 && dalle::conv_in_rgb(images.data_ptr<float>(), w.data_ptr(), bias.data_ptr<float>(), y.data_ptr(), N, H, W, Cout,
+                                          cur_stream()), "conv_in_rgb: unsupported shape (Cout % 128, H*W % 128)");
+  return y;
+}
+
+// out (M) int64 = argmax_j (x_m . w_j + bias_j); x (M, K) bf16, w (V, K) bf16, bias (V) fp32; ties -> lowest index
+Tensor linear_argmax(Tensor x, Tensor w, Tensor bias) {
+  CHECK_IN(x, torch::kBFloat16); CHECK_IN(w, torch::kBFloat16); CHECK_IN(bias, torch::kFloat32);
+  TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && x.size(1) == w.size(1) && bias.numel() == w.size(0),
+              "linear_argmax: x (M, K), w (V, K), bias (V)");
+  const long M = x.size(0);
+  auto out = torch::empty({M}, x.options().dtype(torch::kInt64));
+  TORCH_CHECK(M > 0 && dalle::linear_argmax(x.data_ptr(), w.data_ptr(), bias.data_ptr<float>(), out.data_ptr<int64_t>(), M,
+                                            (int)x.size(1), (int)w.size(0), cur_stream()),
+              "linear_argmax: unsupported shape (M >= 1, K % 64, V % 128)");
+  return out;
 }
 
 std::vector<Tensor> gn_stats(Tensor x, double eps) {
@@ -1249,7 +1282,8 @@ void decode_attn_(Tensor q, Tensor kc, Tensor vc, Tensor out, Tensor pos, int64_
 // Fused sampler. Returns the raw samples (B,); with text/codes/tok given it also does the decode-step
 // bookkeeping at device position *pos (codes[:, pos - T + 1] = sample, tok = next input token).
 Tensor sample_step(Tensor logits, int64_t top_k, double top_p, double temperature, Tensor seed, Tensor pos,
-                   c10::optional<Tensor> text, c10::optional<Tensor> codes, c10::optional<Tensor> tok, int64_t vt) {
+                   c10::optional<Tensor> text, c10::optional<Tensor> codes, c10::optional<Tensor> tok, int64_t vt,
+                   c10::optional<Tensor> prime, c10::optional<Tensor> n_prime) {
   CHECK_IN(logits, torch::kFloat32); CHECK_IN(seed, torch::kInt64); CHECK_IN(pos, torch::kInt32);
   TORCH_CHECK(logits.dim() == 2 && logits.size(1) >= 1 && logits.size(1) <= 8192, "sample: logits must be (B, V <= 8192)");
   TORCH_CHECK(seed.numel() == 1 && pos.numel() == 1, "sample: seed / pos are device scalars");
@@ -1275,6 +1309,15 @@ Tensor sample_step(Tensor logits, int64_t top_k, double top_p, double temperatur
     a.codes = codes->data_ptr<int64_t>();
     a.img_len = codes->size(1);
     a.tok = tok->data_ptr<int64_t>();
+  }
+  TORCH_CHECK(prime.has_value() == n_prime.has_value(), "sample: give prime and n_prime together");
+  if (prime.has_value()) {
+    TORCH_CHECK(book, "sample: prime needs text, codes and tok");
+    CHECK_IN((*prime), torch::kInt64); CHECK_IN((*n_prime), torch::kInt32);
+    TORCH_CHECK(prime->dim() == 2 && prime->size(0) == B && prime->size(1) == a.img_len && n_prime->numel() == 1,
+                "sample: prime (B, image_len), n_prime a device scalar");
+    a.prime = prime->data_ptr<int64_t>();
+    a.n_prime = n_prime->data_ptr<int>();
   }
   auto out = torch::empty({B}, logits.options().dtype(torch::kInt64));
   a.sampled = out.data_ptr<int64_t>();
@@ -1439,7 +1482,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("xent_colsum_", &xent_colsum_);
   m.def("conv3x3", &conv3x3, py::arg("x"), py::arg("w"), py::arg("bias") = py::none(), py::arg("res") = py::none(),
         py::arg("mean") = py::none(), py::arg("rstd") = py::none(), py::arg("gamma") = py::none(), py::arg("beta") = py::none(),
-        py::arg("ups") = false);
+        py::arg("ups") = false, py::arg("down") = false);
+  m.def("conv_in_rgb", &conv_in_rgb);
+  m.def("linear_argmax", &linear_argmax);
   m.def("gn_stats", &gn_stats);
   m.def("gn_apply", &gn_apply, py::arg("x"), py::arg("mean"), py::arg("rstd"), py::arg("gamma"), py::arg("beta"),
         py::arg("silu") = false);
@@ -1474,7 +1519,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("vq_embed", &vq_embed);
   m.def("sample_step", &sample_step, py::arg("logits"), py::arg("top_k"), py::arg("top_p"), py::arg("temperature"),
         py::arg("seed"), py::arg("pos"), py::arg("text") = py::none(), py::arg("codes") = py::none(),
-        py::arg("tok") = py::none(), py::arg("vt") = 0);
+        py::arg("tok") = py::none(), py::arg("vt") = 0, py::arg("prime") = py::none(), py::arg("n_prime") = py::none());
   m.def("lamb_grad_norm", &lamb_grad_norm);
   m.def("lamb_step", &lamb_step);
 }

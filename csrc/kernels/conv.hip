@@ -1,5 +1,6 @@
-// VQGAN decoder on CDNA4 (reference: taming-transformers Decoder, run by
-// inference/run_inference.py:122-123 through VQGanVAE.decode). Activations are NHWC bf16.
+// VQGAN decoder and encoder on CDNA4 (reference: taming-transformers Decoder / Encoder, run by
+// inference/run_inference.py:122-123 through VQGanVAE.decode, and by VQGanVAE.get_codebook_indices). Activations
+// are NHWC bf16. The encoder adds a stride-2 gather mode of conv3x3 (Downsample), conv_in_rgb and linear_argmax.
 //
 // * conv3x3_kernel: 3x3 / stride 1 / pad 1 convolution as an implicit GEMM on MFMA
 //     Y[p, co] = sum_{tap, ci} X'[shift_tap(p), ci] * W[co, tap, ci]   (+ bias, + residual)
@@ -32,6 +33,9 @@ __device__ __forceinline__ int cv_idx(int row, int col) { return row * 64 + ((((
 
 __device__ __forceinline__ float silu(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-v * LOG2E)); }
 
+// DOWN (compile time): taming's Downsample, zero pad (0, 1, 0, 1) then stride 2 / pad 0: output pixel (y, x) gathers
+// source (2y + ky, 2x + kx) of the (2H, 2W) input, zero where the index reaches 2H / 2W (no GroupNorm, no residual).
+template <bool DOWN>
 __global__ __launch_bounds__(CV_THREADS, 2) void conv3x3_kernel(ConvArgs a) {
   __shared__ __attribute__((aligned(16))) __bf16 smem[2 * 2 * CV_BM * CV_BK];  // [buf][A | B], 64 KiB
   __shared__ float gsc[1024], gsh[1024];                                      // GN scale / shift per channel
@@ -64,7 +68,7 @@ __global__ __launch_bounds__(CV_THREADS, 2) void conv3x3_kernel(ConvArgs a) {
     py[i] = rem / a.W;
     px[i] = rem - py[i] * a.W;
   }
-  const int Hs = a.ups ? a.H >> 1 : a.H, Ws = a.ups ? a.W >> 1 : a.W;
+  const int Hs = DOWN ? a.H * 2 : a.ups ? a.H >> 1 : a.H, Ws = DOWN ? a.W * 2 : a.ups ? a.W >> 1 : a.W;
   const int cchunks = a.Cin / CV_BK;
   const int nk = 9 * cchunks;
   s16x8 ra[4], rb[4];
@@ -75,8 +79,14 @@ __global__ __launch_bounds__(CV_THREADS, 2) void conv3x3_kernel(ConvArgs a) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       int yy = py[i] + dy, xx = px[i] + dx;
-      va[i] = yy >= 0 && yy < a.H && xx >= 0 && xx < a.W;
-      if (a.ups) { yy >>= 1; xx >>= 1; }
+      if (DOWN) {
+        yy = 2 * py[i] + dy + 1;
+        xx = 2 * px[i] + dx + 1;
+        va[i] = yy < Hs && xx < Ws;
+      } else {
+        va[i] = yy >= 0 && yy < a.H && xx >= 0 && xx < a.W;
+        if (a.ups) { yy >>= 1; xx >>= 1; }
+      }
       const size_t off = (((size_t)img * Hs + (va[i] ? yy : 0)) * Ws + (va[i] ? xx : 0)) * a.Cin + c0 + lch * 8;
       ra[i] = *reinterpret_cast<const s16x8*>(X + off);
       rb[i] = *reinterpret_cast<const s16x8*>(Wt + (size_t)(n0 + lrow + 32 * i) * (9 * a.Cin) + tap * a.Cin + c0 + lch * 8);
@@ -177,6 +187,199 @@ __global__ __launch_bounds__(CV_THREADS, 2) void conv3x3_kernel(ConvArgs a) {
       for (int j = 0; j < 8; ++j) f[j] += r8[j];
     }
     *reinterpret_cast<s16x8*>(Y + o) = pack8(f);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Encoder input conv: images (N, 3, H, W) fp32 NCHW in [0, 1] -> (N, H, W, Cout) bf16 NHWC. The encoder's 2x - 1
+// rescale is fused: x' = bf16(fp32(2x - 1)), zero padded, then 3x3 / stride 1 / pad 1 in fp32 (+ bias), one rounding.
+// K = 27 is far too thin for the MFMA tiles, so this is a VALU kernel over an LDS im2col of the workgroup's 128
+// pixels (27 values each) with the 128-channel weight slice in LDS as fp32; it is bound by its 256-B-per-pixel output
+// store: a thread owns one 8-channel run (a 16-byte store) of 8 pixels, and 16 lanes write a pixel's 256 bytes.
+constexpr int CI_BM = 128, CI_BN = 128, CI_K = 27, CI_LD = 29;  // odd row stride: the im2col writes spread over the banks
+__global__ __launch_bounds__(256) void conv_in_rgb_kernel(const float* __restrict__ img, const __bf16* __restrict__ w,
+                                                          const float* __restrict__ bias, __bf16* __restrict__ y, int H, int W,
+                                                          int Cout) {
+  __shared__ __attribute__((aligned(16))) float wl[CI_K * CI_BN];  // [k][channel]
+  __shared__ float xs[CI_BM * CI_LD];                               // [pixel][k = tap * 3 + c]
+  const int tid = threadIdx.x;
+  const long HW = (long)H * W;
+  const int tiles_n = Cout / CI_BN;
+  const long tm = blockIdx.x / tiles_n;
+  const int n0 = (int)(blockIdx.x - tm * tiles_n) * CI_BN;
+  const long m0 = tm * CI_BM;
+  const long n = m0 / HW;  // a tile never spans two images (HW % 128 == 0)
+  const int p0 = (int)(m0 - n * HW);
+  for (int e = tid; e < CI_K * CI_BN; e += 256) {
+    const int c = e / CI_K, k = e - c * CI_K;
+    wl[k * CI_BN + c] = (float)w[(size_t)(n0 + c) * CI_K + k];
+  }
+  for (int e = tid; e < CI_BM * CI_K; e += 256) {
+    const int k = e / CI_BM, pix = e - k * CI_BM;  // consecutive lanes: consecutive pixels of one plane
+    const int tap = k / 3, c = k - tap * 3;
+    const int p = p0 + pix;
+    const int py = p / W, px = p - py * W;
+    const int sy = py + tap / 3 - 1, sx = px + (tap - (tap / 3) * 3) - 1;
+    float v = 0.f;
+    if (sy >= 0 && sy < H && sx >= 0 && sx < W) {
+      const float x = img[((size_t)n * 3 + c) * HW + (size_t)sy * W + sx];
+      v = bf2f(f2bf(2.0f * x - 1.0f));
+    }
+    xs[pix * CI_LD + k] = v;
+  }
+  __syncthreads();
+  const int ch = tid & 15, prow = tid >> 4;
+  float acc[8][8];
+  {
+    const f32x4 b0 = *reinterpret_cast<const f32x4*>(bias + n0 + ch * 8), b1 = *reinterpret_cast<const f32x4*>(bias + n0 + ch * 8 + 4);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      acc[i][0] = b0[0]; acc[i][1] = b0[1]; acc[i][2] = b0[2]; acc[i][3] = b0[3];
+      acc[i][4] = b1[0]; acc[i][5] = b1[1]; acc[i][6] = b1[2]; acc[i][7] = b1[3];
+    }
+  }
+#pragma unroll 3
+  for (int k = 0; k < CI_K; ++k) {
+    const f32x4 w0 = *reinterpret_cast<const f32x4*>(wl + k * CI_BN + ch * 8);
+    const f32x4 w1 = *reinterpret_cast<const f32x4*>(wl + k * CI_BN + ch * 8 + 4);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const float xv = xs[(prow + 16 * i) * CI_LD + k];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        acc[i][j] = fmaf(xv, w0[j], acc[i][j]);
+        acc[i][4 + j] = fmaf(xv, w1[j], acc[i][4 + j]);
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 8; ++i)
+    *reinterpret_cast<s16x8*>(y + (size_t)(m0 + prow + 16 * i) * Cout + n0 + ch * 8) = pack8(acc[i]);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Fused projection + argmax (the VQGAN quantisers): out[m] = argmax_j (x_m . w_j + bias_j), x (M, K), w (V, K) bf16,
+// fp32 accumulation on MFMA with conv3x3's tile code (128 rows x 128 columns, K-step 64, register-staged double
+// buffer, swizzled LDS rows). A workgroup owns 128 rows and walks ALL V / 128 column tiles, each lane keeping a
+// running (max, index) for the 16 rows of its accumulators, so the (M, V) matrix never exists in memory. Every
+// comparison is (value greater) or (value equal and index lower): exact ties go to the lowest index in any order
+// of evaluation; the 16 lanes that share a row and then the two column waves are folded with that same rule.
+// Rows beyond M read row M - 1 and are not written.
+__global__ __launch_bounds__(CV_THREADS, 2) void linear_argmax_kernel(const __bf16* __restrict__ X, const __bf16* __restrict__ Wt,
+                                                                      const float* __restrict__ bias, int64_t* __restrict__ out,
+                                                                      long M, int K, int V) {
+  __shared__ __attribute__((aligned(16))) __bf16 smem[2 * 2 * CV_BM * CV_BK];  // [buf][A | B], 64 KiB
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int wm = wave >> 1, wn = wave & 1;
+  const int fr = lane & 15, fq = lane >> 4;
+  const long m0 = (long)blockIdx.x * CV_BM;
+  const int lrow = tid >> 3, lch = tid & 7;
+  const int ksteps = K / CV_BK;
+  const int nk = (V / CV_BN) * ksteps;
+  const __bf16* xrow[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) xrow[i] = X + (size_t)min(m0 + lrow + 32 * i, M - 1) * K + lch * 8;
+  s16x8 ra[4], rb[4];
+  auto load = [&](int s) {
+    const int tn = s / ksteps, k0 = (s - tn * ksteps) * CV_BK;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      ra[i] = *reinterpret_cast<const s16x8*>(xrow[i] + k0);
+      rb[i] = *reinterpret_cast<const s16x8*>(Wt + (size_t)(tn * CV_BN + lrow + 32 * i) * K + k0 + lch * 8);
+    }
+  };
+  auto store = [&](int buf) {
+    __bf16* As = smem + buf * (2 * CV_BM * CV_BK);
+    __bf16* Bs = As + CV_BM * CV_BK;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int row = lrow + 32 * i;
+      *reinterpret_cast<s16x8*>(As + cv_idx(row, lch * 8)) = ra[i];
+      *reinterpret_cast<s16x8*>(Bs + cv_idx(row, lch * 8)) = rb[i];
+    }
+  };
+  f32x4 acc[4][4];
+  float best[4][4];
+  int besti[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+      best[i][j] = -INFINITY;  // [i][r]: row wm * 64 + i * 16 + fq * 4 + r
+      besti[i][j] = 0;
+    }
+  load(0);
+  store(0);
+  __syncthreads();
+  for (int s = 0; s < nk; ++s) {
+    const int buf = s & 1;
+    if (s + 1 < nk) load(s + 1);
+    const __bf16* As = smem + buf * (2 * CV_BM * CV_BK);
+    const __bf16* Bs = As + CV_BM * CV_BK;
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+      bf16x8 fa[4], fb[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        fa[i] = *reinterpret_cast<const bf16x8*>(As + cv_idx(wm * 64 + i * 16 + fr, (kk * 4 + fq) * 8));
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        fb[j] = *reinterpret_cast<const bf16x8*>(Bs + cv_idx(wn * 64 + j * 16 + fr, (kk * 4 + fq) * 8));
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
+    }
+    const int tn = s / ksteps;
+    if (s - tn * ksteps == ksteps - 1) {  // the column tile is complete: fold it into the running maxima
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int col = tn * CV_BN + wn * 64 + j * 16 + fr;
+        const float bj = bias[col];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const float v = acc[i][j][r] + bj;
+            if (v > best[i][r] || (v == best[i][r] && col < besti[i][r])) { best[i][r] = v; besti[i][r] = col; }
+          }
+          acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+      }
+    }
+    if (s + 1 < nk) store(buf ^ 1);
+    __syncthreads();
+  }
+  // fold the 16 lanes (fr) that hold the same rows, then the two column waves through LDS
+  float* redv = reinterpret_cast<float*>(smem);       // [wn][128 rows]
+  int* redi = reinterpret_cast<int*>(smem) + 2 * CV_BM;
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      float b = best[i][r];
+      int bi = besti[i][r];
+#pragma unroll
+      for (int o = 1; o < 16; o <<= 1) {
+        const float ob = __shfl_xor(b, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        if (ob > b || (ob == b && oi < bi)) { b = ob; bi = oi; }
+      }
+      if (fr == 0) {
+        const int row = wm * 64 + i * 16 + fq * 4 + r;
+        redv[wn * CV_BM + row] = b;
+        redi[wn * CV_BM + row] = bi;
+      }
+    }
+  __syncthreads();
+  if (tid < CV_BM && m0 + tid < M) {
+    float b = redv[tid];
+    int bi = redi[tid];
+    const float ob = redv[CV_BM + tid];
+    const int oi = redi[CV_BM + tid];
+    if (ob > b || (ob == b && oi < bi)) { b = ob; bi = oi; }
+    out[m0 + tid] = (int64_t)bi;
   }
 }
 
@@ -370,8 +573,26 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* __restri
 bool conv3x3(const ConvArgs& a, hipStream_t st) {
   if (a.Cin % CV_BK || a.Cout % CV_BN || (a.H * a.W) % CV_BM || a.Cin > 1024) return false;
   if (a.ups && ((a.H & 1) || (a.W & 1))) return false;
+  if (a.down && (a.ups || a.gn || a.res != nullptr)) return false;
   const int tiles = (a.N * a.H * a.W / CV_BM) * (a.Cout / CV_BN);
-  hipLaunchKernelGGL(conv3x3_kernel, dim3(tiles), dim3(CV_THREADS), 0, st, a);
+  if (a.down)
+    hipLaunchKernelGGL(conv3x3_kernel<true>, dim3(tiles), dim3(CV_THREADS), 0, st, a);
+  else
+    hipLaunchKernelGGL(conv3x3_kernel<false>, dim3(tiles), dim3(CV_THREADS), 0, st, a);
+  return true;
+}
+
+bool conv_in_rgb(const float* img, const void* w, const float* bias, void* y, int N, int H, int W, int Cout, hipStream_t st) {
+  if (N < 1 || Cout % CI_BN || ((long)H * W) % CI_BM) return false;
+  const long tiles = ((long)N * H * W / CI_BM) * (Cout / CI_BN);
+  hipLaunchKernelGGL(conv_in_rgb_kernel, dim3(tiles), dim3(256), 0, st, img, (const __bf16*)w, bias, (__bf16*)y, H, W, Cout);
+  return true;
+}
+
+bool linear_argmax(const void* x, const void* w, const float* bias, int64_t* out, long M, int K, int V, hipStream_t st) {
+  if (M < 1 || K < CV_BK || K % CV_BK || V < CV_BN || V % CV_BN) return false;
+  hipLaunchKernelGGL(linear_argmax_kernel, dim3((M + CV_BM - 1) / CV_BM), dim3(CV_THREADS), 0, st, (const __bf16*)x,
+                     (const __bf16*)w, bias, out, M, K, V);
   return true;
 }
 

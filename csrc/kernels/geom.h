@@ -31,7 +31,7 @@ struct ShiftGeom {
   int S;      // image side
   int shift;  // 0 = plain LayerNorm
 };
-// VQGAN decoder 3x3 convolution (conv.hip): bf16 tensors passed as void pointers (host-compiled header)
+// VQGAN 3x3 convolution (conv.hip): bf16 tensors passed as void pointers (host-compiled header)
 struct ConvArgs {
   const void* x;       // [N, Hs, Ws, Cin] NHWC (Hs = H / 2 when ups)
   const void* w;       // [Cout, 9 * Cin] tap-major, channel-contiguous
@@ -43,6 +43,7 @@ struct ConvArgs {
   const float* gamma;  // [Cin]
   const float* beta;   // [Cin]
   int N, H, W, Cin, Cout, ups, gn;
+  int down;            // stride-2 Downsample: x is [N, 2H, 2W, Cin], zero pad right / bottom (no ups / gn / res)
 };
 
 // Destination of a column-reduced parameter gradient (see column_sum_kernel)
@@ -105,6 +106,8 @@ struct SampleArgs {
   int64_t* codes;       // (B, img_len), may be null
   int64_t* tok;         // (B,) next input token, may be null
   int64_t* sampled;     // (B,) the raw sample, may be null
+  const int64_t* prime; // (B, img_len) forced image codes, may be null
+  const int* n_prime;   // device scalar: image positions [0, *n_prime) take prime's code instead of the sample
 };
 
 }  // namespace dalle

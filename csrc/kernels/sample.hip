@@ -14,7 +14,9 @@
 //   * the uniforms come from a counter-based hash of (seed, position, row, token) -- replay-safe inside
 //     a captured graph (the position is read from device memory) and deterministic for a seed.
 // Finally thread 0 writes the image code of this position and the next input token (the next caption
-// token during prefill, else the sample shifted into the image vocabulary).
+// token during prefill, else the sample shifted into the image vocabulary). With a `prime` table the first
+// *n_prime image positions take the table's code in place of the sample (image-primed generation; the count is
+// a device scalar, so one captured graph serves every prefix length).
 #include "common.h"
 #include "geom.h"
 
@@ -226,7 +228,11 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(SampleArgs a) {
   if (tid == 0) {
     for (int w = 1; w < SMP_NW; ++w)
       if (redf[w] > best || (redf[w] == best && redi[w] < besti)) { best = redf[w]; besti = redi[w]; }
-    const int64_t nxt = besti;
+    int64_t nxt = besti;
+    if (a.prime != nullptr) {  // forced prefix: image position ci < *n_prime takes the given code, not the sample
+      const int ci = pos - (a.T - 1);
+      if (ci >= 0 && ci < min(*a.n_prime, a.img_len)) nxt = a.prime[(size_t)row * a.img_len + ci];
+    }
     if (a.sampled) a.sampled[row] = nxt;
     if (a.codes) {
       const int ci = min(max(pos - (a.T - 1), 0), a.img_len - 1);

@@ -297,17 +297,39 @@ class DALLE(nn.Module):
                         num_init_img_tokens=None, top_k: int = 0, top_p: float = 1.0, use_cache: bool = True,
                         return_codes: bool = False, use_graph=None):
         """Sample 1024 image tokens per caption with the KV-cache decoder (hipGraph-replayed on MI355X)
-        and decode them with ``self.vae`` to (b, 3, H, W) images in [0, 1] (codes if no VAE)."""
+        and decode them with ``self.vae`` to (b, 3, H, W) images in [0, 1] (codes if no VAE).
+
+        ``img`` primes the generation (dalle-pytorch's image completion / variations): a (b, 3, S, S) float
+        picture in [0, 1] is encoded with ``self.vae.get_codebook_indices``; a 2-D integer tensor is taken as image
+        codes (works without a VAE). Its first ``num_init_img_tokens`` codes (default ``int(0.4375 *
+        image_seq_len)``, as dalle-pytorch) are forced as the first image tokens and the rest is sampled."""
         from .generation import make_decode_engine
 
         if filter_thres is not None and not top_k:
             top_k = max(1, int((1 - filter_thres) * self.num_image_tokens))
         text_bos = self.prepare_text(text)
+        prime = None
+        if img is not None:
+            k = int(0.4375 * self.image_seq_len) if num_init_img_tokens is None else int(num_init_img_tokens)
+            if not 0 <= k < self.image_seq_len:
+                raise ValueError(f"num_init_img_tokens must be in [0, {self.image_seq_len}), got {k}")
+            if img.dim() == 4:
+                if self.vae is None:
+                    raise ValueError("priming with a raw image needs a VAE; pass image codes (b, n) instead")
+                img = self.vae.get_codebook_indices(img)
+            elif img.dim() != 2 or img.dtype.is_floating_point:
+                raise ValueError("img must be (b, 3, S, S) float images or (b, n) integer image codes")
+            if img.shape[0] != text.shape[0]:
+                raise ValueError(f"img batch {img.shape[0]} does not match the text batch {text.shape[0]}")
+            if img.shape[1] < k:
+                raise ValueError(f"img holds {img.shape[1]} codes, fewer than the {k} to prime with")
+            prime = img[:, :k].long().to(text.device)
         eng = getattr(self, "_decode_engine", None)
         if eng is None or eng.B != text.shape[0] or eng.device != text.device:
             eng = make_decode_engine(self, text.shape[0], device=text.device)
             self._decode_engine = eng
-        codes = eng.generate(text_bos, temperature=temperature, top_k=top_k, top_p=top_p, use_graph=use_graph)
+        kw = {} if prime is None else {"prime": prime}
+        codes = eng.generate(text_bos, temperature=temperature, top_k=top_k, top_p=top_p, use_graph=use_graph, **kw)
         if return_codes or self.vae is None:
             return codes
         return self.vae.decode(codes)

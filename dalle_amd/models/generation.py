@@ -95,6 +95,10 @@ class DecodeEngine:
         # fused HIP sampler (K18); its Gumbel noise is a counter hash of (seed, position, row, token)
         self.fused_sampler = use_hip and fused_sampler
         self.seed = torch.zeros((), dtype=torch.int64, device=dev)
+        # forced prefix (image-primed generation): image positions [0, n_prime) take prime's code instead of the
+        # sample. Both live on the device, so one captured graph serves every prefix length, 0 included
+        self.prime = torch.zeros(B, cfg.image_seq_len, dtype=torch.long, device=dev)
+        self.n_prime = torch.zeros((), dtype=torch.int32, device=dev)
         self.graph = None
         self._pf_graphs = {}  # captured caption prefills, by (rows, input buffer)
         self._pf_masks = {}   # contiguous (P, P) caption blocks of the layer patterns
@@ -142,6 +146,7 @@ class DecodeEngine:
         """Zero position/caches and refresh the compute-dtype weight copies IN PLACE (a captured graph
         keeps pointing at the same buffers, so weight updates between calls are still seen)."""
         self.pos.zero_()
+        self.n_prime.zero_()
         if self._refresh_weights:
             for p, w in self._w.values():
                 w.copy_(p.detach().reshape(w.shape))
@@ -343,13 +348,16 @@ class DecodeEngine:
             # one HIP launch (csrc/kernels/sample.hip): filter + sample + codes / next-token bookkeeping
             from ..ops.hip_ops import C
             C().sample_step(logits, int(self.top_k or 0), float(1.0 if self.top_p is None else self.top_p),
-                            float(self.temperature), self.seed, self.pos, self.text_bos, self.codes, self.tok, self.Vt)
+                            float(self.temperature), self.seed, self.pos, self.text_bos, self.codes, self.tok, self.Vt,
+                            prime=self.prime, n_prime=self.n_prime)
             self.pos.add_(1)
             return logits
         logits = filter_logits(logits, self.top_k, self.top_p)
         nxt = gumbel_sample(logits, self.temperature)
         p = self.pos.long()
-        idx = (p - (self.T - 1)).clamp(0, self.cfg.image_seq_len - 1).view(1, 1).expand(self.B, 1)
+        ci = p - (self.T - 1)
+        idx = ci.clamp(0, self.cfg.image_seq_len - 1).view(1, 1).expand(self.B, 1)
+        nxt = torch.where((ci >= 0) & (ci < self.n_prime), self.prime.gather(1, idx).view(self.B), nxt)
         self.codes.scatter_(1, idx, nxt.view(self.B, 1))
         nxt_text = self.text_bos.gather(1, (p + 1).clamp(max=self.T - 1).view(1, 1).expand(self.B, 1)).view(self.B)
         self.tok.copy_(torch.where(p + 1 < self.T, nxt_text, nxt + self.Vt))
@@ -369,6 +377,22 @@ class DecodeEngine:
             self.text_shared.copy_((text_bos == text_bos[:1]).all().view(1))
         else:
             self.text_shared.zero_()
+
+    def set_prime(self, prime: Optional[torch.Tensor]):
+        """Force the first ``k`` image tokens of the steps that follow to ``prime`` (B, k), 0 <= k < image_seq_len
+        (None: no prefix). ``reset`` clears the count, so this goes after the last reset of a call."""
+        if prime is None:
+            self.n_prime.zero_()
+            return
+        L = self.cfg.image_seq_len
+        if prime.dim() != 2 or prime.shape[0] != self.B or not 0 <= prime.shape[1] < L:
+            raise ValueError(f"prime must be (batch {self.B}, k) with 0 <= k < {L}, got {tuple(prime.shape)}")
+        if prime.dtype.is_floating_point or prime.dtype == torch.bool:
+            raise ValueError("prime must hold integer image codes")
+        k = prime.shape[1]
+        if k:
+            self.prime[:, :k].copy_(prime)
+        self.n_prime.fill_(k)
 
     @torch.no_grad()
     def prefill(self, text_bos: torch.Tensor):
@@ -540,11 +564,14 @@ class DecodeEngine:
 
     @torch.no_grad()
     def generate(self, text_bos: torch.Tensor, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
-                 use_graph: Optional[bool] = None, seed: Optional[int] = None, parallel_prefill: Optional[bool] = None) -> torch.Tensor:
+                 use_graph: Optional[bool] = None, seed: Optional[int] = None, parallel_prefill: Optional[bool] = None,
+                 prime: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The caption prefill (one batched pass per layer, ``parallel_prefill``, default on; else T-1
         decode steps) then the 1024 sampled image tokens through one step function; on MI355X that step
         is a single hipGraph replayed per position. ``seed`` fixes the fused sampler's noise (default:
-        drawn from torch's global generator)."""
+        drawn from torch's global generator). ``prime`` (B, k) image codes: the first ``k`` image tokens are
+        forced to them (ordinary decode steps whose sample is replaced) and the rest sampled; the noise stays a
+        function of (seed, position, row, token), so positions >= k draw what an unprimed call draws there."""
         self.temperature, self.top_k, self.top_p = temperature, top_k, top_p
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
@@ -561,6 +588,7 @@ class DecodeEngine:
             steps = self.n - (self.T - 1)
         else:
             self._start(text_bos)
+        self.set_prime(prime)  # after the last reset (``_start`` above, or the one inside ``prefill_parallel``)
         for _ in range(steps):
             if use_graph:
                 self.graph.replay()
@@ -731,7 +759,10 @@ class SplitDecodeEngine:
 
     @torch.no_grad()
     def generate(self, text_bos: torch.Tensor, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
-                 use_graph: Optional[bool] = None, seed: Optional[int] = None) -> torch.Tensor:
+                 use_graph: Optional[bool] = None, seed: Optional[int] = None,
+                 prime: Optional[torch.Tensor] = None) -> torch.Tensor:
+        if prime is not None and (prime.dim() != 2 or prime.shape[0] != self.B):
+            raise ValueError(f"prime must be (batch {self.B}, k), got {tuple(prime.shape)}")
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         for i, p in enumerate(self.parts):
@@ -743,6 +774,9 @@ class SplitDecodeEngine:
         if use_graph:
             self._capture()
         self.prefill_parallel(text_bos)
+        b = self.B // self.nparts
+        for i, p in enumerate(self.parts):  # after the parts' last reset (inside ``prefill_parallel``)
+            p.set_prime(None if prime is None else prime[i * b:(i + 1) * b])
         steps = n - (self.parts[0].T - 1)
         if use_graph:
             self.replay_steps(steps)

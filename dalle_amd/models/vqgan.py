@@ -7,6 +7,8 @@ swish, nearest x2 upsampling, attention at the 32x32 resolution) -> ``(clamp(-1,
 conv encoder (stride-2 downsampling, same blocks) -> ``quant_conv`` -> code selection: the Gumbel
 quantizer's ``proj`` logits (argmax = the mode; ``gumbel_tau`` > 0 samples like taming's eval-time
 ``gumbel_softmax(hard=True)``), or the nearest codebook vector for a plain VQ checkpoint.
+On MI355X the mode (``gumbel_tau == 0``) runs on the HIP encoder of ``vqgan_hip.py`` (``hip_encoder``), whose fused
+projection + argmax never builds the (pixels, codes) logit / distance matrix.
 Parameter names follow taming's ``VQModel`` / ``GumbelVQ`` so a real checkpoint's state dict loads
 (``torch.load(weights_only=True)``); without a checkpoint the decoder is random-init (benchmarks).
 Default config = the LAION ``vqgan_gumbel_f8`` one: 8192 codes x 256 dims, ch 128, ch_mult
@@ -263,6 +265,25 @@ class VQGanVAE(nn.Module):
             self._hip_decoder = HipDecoder(self.post_quant_conv, self.decoder)
         return True
 
+    hip_encoder = True  # False: the PyTorch / MIOpen encoder (numerics A/B in tests/test_vqgan_encoder_gpu.py)
+
+    def use_hip_encoder(self, h: Optional[int] = None, w: Optional[int] = None) -> bool:
+        """True when ``get_codebook_indices`` runs on the HIP kernels (MI355X, supported channel layout and quantiser,
+        ``hip_encoder``); with ``h, w`` also whether pictures of that size do: sides the levels cannot halve or a
+        latent grid the conv kernel cannot tile (40 x 40 pictures) go to the PyTorch encoder for that call, and the
+        cached ``HipEncoder`` stays for the next."""
+        if not self.hip_encoder:
+            return False
+        from .vqgan_hip import HipEncoder, encoder_grid_supported, supported_encoder
+
+        if h is not None and not encoder_grid_supported(self.encoder, h, w if w is not None else h):
+            return False
+        if getattr(self, "_hip_encoder", None) is None:
+            if not supported_encoder(self.encoder, self.quant_conv, self.quantize):
+                return False
+            self._hip_encoder = HipEncoder(self.encoder, self.quant_conv, self.quantize)
+        return True
+
     def _codebook_bf16(self) -> torch.Tensor:
         cb = self.codebook
         key = (cb.data_ptr(), cb._version)
@@ -276,6 +297,10 @@ class VQGanVAE(nn.Module):
         """(B, 3, H, W) images in [0, 1] -> (B, (H/f)^2) code indices (dalle-pytorch ``VQGanVAE`` API)."""
         if not getattr(self, "has_encoder", True):
             raise RuntimeError("this VQGAN checkpoint holds no encoder weights")
+        if images.is_cuda and images.dim() == 4 and not gumbel_tau > 0 and self.use_hip_encoder(images.shape[2], images.shape[3]):
+            # K19 on the hand-written HIP kernels (models/vqgan_hip.py): the mode of the quantiser, no (pixels, codes)
+            # logit / distance matrix
+            return self._hip_encoder(images)
         h = self.quant_conv(self.encoder(2 * images - 1))
         if self.quantize.proj is not None:
             logits = self.quantize.proj(h)

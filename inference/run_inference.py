@@ -65,14 +65,37 @@ def normalize_state_dict_keys(state_dict):
     return out
 
 
-def generate(query, *, tokenizer, model, batch_size, n_iters, temperature, top_k, top_p, text_seq_len=256, device="cuda"):
+def load_init_image(path: str, image_size: int) -> torch.Tensor:
+    """A picture file -> (3, S, S) float tensor in [0, 1]: short side resized to ``image_size``, centre crop."""
+    from PIL import Image
+
+    im = Image.open(path).convert("RGB")
+    w, h = im.size
+    scale = image_size / min(w, h)
+    w2, h2 = max(image_size, round(w * scale)), max(image_size, round(h * scale))
+    im = im.resize((w2, h2), Image.BICUBIC)
+    left, top = (w2 - image_size) // 2, (h2 - image_size) // 2
+    im = im.crop((left, top, left + image_size, top + image_size))
+    return torch.from_numpy(np.asarray(im, dtype=np.float32) / 255.0).permute(2, 0, 1).contiguous()
+
+
+def generate(query, *, tokenizer, model, batch_size, n_iters, temperature, top_k, top_p, text_seq_len=256, device="cuda",
+             init_image=None, num_init_img_tokens=None):
+    """``init_image``: a (3, S, S) picture in [0, 1] (repeated over the batch) or (b, ...) images / codes, whose first
+    ``num_init_img_tokens`` VQGAN codes every sample starts from (``DALLE.generate_images(img=...)``)."""
     ids = tokenizer(query, add_special_tokens=False, max_length=text_seq_len, truncation=True)['input_ids']
     input_ids = torch.full((text_seq_len,), 1, dtype=torch.long)
     input_ids[: len(ids)] = torch.tensor(ids, dtype=torch.long)
     input_ids = input_ids.repeat(batch_size, 1).to(device)
+    prime = {}
+    if init_image is not None:
+        if init_image.dim() == 3:
+            init_image = init_image.unsqueeze(0).repeat(batch_size, 1, 1, 1)
+        prime = dict(img=init_image.to(device), num_init_img_tokens=num_init_img_tokens)
     result = []
     for _ in range(n_iters):
-        output = model.model.generate_images(input_ids, temperature=temperature, top_k=top_k, top_p=top_p, use_cache=True)
+        output = model.model.generate_images(input_ids, temperature=temperature, top_k=top_k, top_p=top_p, use_cache=True,
+                                             **prime)
         output = output.permute(0, 2, 3, 1).float().cpu().numpy()
         result.extend(output)
     return result
@@ -150,6 +173,10 @@ def main(argv=None):
     parser.add_argument('--clip-tokenizer', type=str, default=None, help='[new] CLIP BPE tokenizer.json (tokenizers format)')
     parser.add_argument('--devices', type=str, default='auto',
                         help='[new] "all" GPUs of the node or a list like "0,1": queries are spread over per-GPU workers')
+    parser.add_argument('--init-image', type=str, default=None,
+                        help='[new] picture whose first VQGAN codes every sample starts from (image completion / variations)')
+    parser.add_argument('--num-init-img-tokens', type=int, default=None,
+                        help='[new] how many codes of --init-image to keep (default: 0.4375 of the image tokens)')
     args = parser.parse_args(argv)
     torch.set_grad_enabled(False)  # inference only (the reference disabled grads at import time)
 
@@ -183,6 +210,8 @@ def main(argv=None):
     else:
         print('[*] No --clip weights: clip_scores will be uniform')
 
+    init_image = load_init_image(args.init_image, gan.image_size) if args.init_image else None
+
     os.makedirs(args.output_dir, exist_ok=True)
     print(f'[*] Saving results to `{args.output_dir}`')
     if len(devices) > 1:
@@ -192,7 +221,8 @@ def main(argv=None):
         model, clip_model, device = ctx
         images = generate(query, tokenizer=tokenizer, model=model, batch_size=args.batch_size, n_iters=args.n_iters,
                           temperature=args.temperature, top_k=args.top_k, top_p=args.top_p,
-                          text_seq_len=model.model.text_seq_len, device=device)
+                          text_seq_len=model.model.text_seq_len, device=device, init_image=init_image,
+                          num_init_img_tokens=args.num_init_img_tokens)
         if clip_model is not None:
             from dalle_amd.models.clip import clip_scores as score_images
 
