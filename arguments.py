@@ -65,6 +65,8 @@ class HFTrainerArguments:
     grad_averaging: str = flag("size_adaptive", "engine only: none | fp16 | 8bit | size_adaptive | powersgd")
     powersgd_rank: int = flag(4, "engine only: rank of the PowerSGD factors")
     backend: Optional[str] = flag(None, "engine only: torch.distributed backend (nccl = RCCL on MI355X, gloo on CPU)")
+    null_cond_prob: float = flag(0.0, "[new] engine only: probability of training a sample on the null caption "
+                                      "(classifier-free guidance; sample with --cond-scale)")
     offload_optimizer_to_host: bool = flag(False, "engine only: optimizer master copy + state in pinned host memory, "
                                                    "stepped on the CPU (default: in HBM, fused HIP LAMB)")
 

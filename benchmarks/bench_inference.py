@@ -31,6 +31,12 @@ def main():
     ap.add_argument("--same-caption", action="store_true",
                     help="one caption repeated over the batch, as inference/run_inference.py generates (the decode "
                          "attention then reads the text keys from one cache row); default: a distinct caption per row")
+    ap.add_argument("--cond-scale", type=float, default=1.0,
+                    help="classifier-free guidance scale: other than 1, a guided engine (two rows per picture; at most 32 "
+                         "pictures stay on the skinny GEMM path)")
+    ap.add_argument("--no-share-src", action="store_true",
+                    help="guided: every row reads the text keys from its own cache (default: null rows from the first "
+                         "null row, caption rows from row 0 when the captions are equal)")
     ap.add_argument("--profile-steps", type=int, default=0,
                     help="batched caption prefill + N image-position decode steps (graph replays unless --no-graph), "
                          "then exit (rocprof)")
@@ -45,14 +51,21 @@ def main():
     text = text.expand(args.batch, -1).contiguous()
     use_graph = not args.no_graph
     from dalle_amd.models.generation import make_decode_engine
-    eng = make_decode_engine(model, args.batch, device=dev)
-    model._decode_engine = eng
+    guided = args.cond_scale != 1.0
+    gen_kw = {"cond_scale": args.cond_scale} if guided else {}
+    eng = make_decode_engine(model, args.batch, device=dev, **({"guided": True} if guided else {}))
+    if guided:
+        model._guided_decode_engine = eng
+        for e in getattr(eng, "parts", [eng]):
+            e.share_src = not args.no_share_src
+    else:
+        model._decode_engine = eng
     parts = getattr(eng, "nparts", 1)
     tb = model.prepare_text(text)
     prefill = getattr(eng, "prefill_parallel", eng.prefill)
     # warm-up generate (captures the step graph)
     t = time.perf_counter()
-    model.generate_images(text, top_k=args.top_k, use_graph=use_graph)
+    model.generate_images(text, top_k=args.top_k, use_graph=use_graph, **gen_kw)
     torch.cuda.synchronize()
     print(f"# warm-up generate done: {time.perf_counter() - t:.2f}s", file=sys.stderr, flush=True)
     t = time.perf_counter()
@@ -70,20 +83,20 @@ def main():
         return
     # one more untimed generate: the first one after the standalone prefill above runs ~0.3 s slow
     # (profiles/r3_decode_partials_cols.txt), which is not the steady-state rate
-    model.generate_images(text, top_k=args.top_k, use_graph=use_graph)
+    model.generate_images(text, top_k=args.top_k, use_graph=use_graph, **gen_kw)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(args.iters):
-        out = model.generate_images(text, top_k=args.top_k, use_graph=use_graph)
+        out = model.generate_images(text, top_k=args.top_k, use_graph=use_graph, **gen_kw)
         torch.cuda.synchronize()
         print(f"# generate {i}: {time.perf_counter() - t0:.2f}s", file=sys.stderr, flush=True)
     el = (time.perf_counter() - t0) / args.iters
     # sampling alone (no VAE): batched caption prefill + 1024 decode steps, per sampled image token
     t2 = time.perf_counter()
-    model.generate_images(text, top_k=args.top_k, use_graph=use_graph, return_codes=True)
+    model.generate_images(text, top_k=args.top_k, use_graph=use_graph, return_codes=True, **gen_kw)
     torch.cuda.synchronize()
     codes_s = time.perf_counter() - t2
-    eng = model._decode_engine
+    eng = model._guided_decode_engine if guided else model._decode_engine
     # decode-only timing: 256 image positions right after the batched caption prefill (every step
     # reads the 256 text keys of each layer's cache plus its local image keys). 256, not 64: the two
     # chains' per-part graphs run free and the window ends on the later one (~19 ms per window,
@@ -108,6 +121,7 @@ def main():
                       "vae": not args.no_vae, "out_shape": list(out.shape), "dtype": "bf16",
                       "captions": "one repeated" if args.same_caption else "distinct per row",
                       "text_shared": [int(e.text_shared.item()) for e in getattr(eng, "parts", [eng])],
+                      **({"cond_scale": args.cond_scale, "rows": 2 * args.batch, "share_src": not args.no_share_src} if guided else {}),
                       "data": "random-init weights, synthetic captions"}), flush=True)
 
 

@@ -70,14 +70,14 @@ void prefill_ln_shift(const float*, const float*, const float*, void*, void*, in
 void prefill_softmax(const float*, const bool*, void*, long, int, hipStream_t);
 void prefill_residual(float*, const void*, const float*, long, int, hipStream_t);
 void decode_attn_part(const float*, int, const float*, const float*, float, void*, void*, void*, const int*, const DecodeGeom&, int,
-                      hipStream_t, const int*);
+                      hipStream_t, const int*, const int*);
 bool skinny_partials(SkinnyArgs, hipStream_t);
 bool skinny_partials_ln(SkinnyArgs, hipStream_t);
 bool skinny_partials_ln_ok(int, int, int);
 int skinny_partials_ks(int, int, int);
 void decode_rope(const void*, const float*, const float*, void*, void*, void*, const int*, const DecodeGeom&, int, float,
                  hipStream_t);
-void decode_attn(const void*, void*, void*, void*, const int*, const DecodeGeom&, int, hipStream_t, const int*);
+void decode_attn(const void*, void*, void*, void*, const int*, const DecodeGeom&, int, hipStream_t, const int*, const int*);
 void vq_embed(const int64_t*, const float*, float*, int, int, int, hipStream_t);
 bool sample_step(const SampleArgs&, hipStream_t);
 bool gemm_geglu_bwd(const void*, const void*, const void*, void*, float*, int, int, int, hipStream_t, int);
@@ -1194,9 +1194,21 @@ static const int* shared_flag(const c10::optional<Tensor>& t) {
   TORCH_CHECK(t->numel() == 1, "text_shared: one int32 flag");
   return t->data_ptr<int>();
 }
+// text_src: optional int32 (B,) device tensor, the batch row whose cache holds each row's text-position K / V
+// (entries are clamped to [0, B) in the kernel); not together with text_shared
+static const int* text_src_rows(const c10::optional<Tensor>& t, const c10::optional<Tensor>& text_shared, int B,
+                                const Tensor& kc) {
+  if (!t.has_value() || !t->defined()) return nullptr;
+  TORCH_CHECK(!(text_shared.has_value() && text_shared->defined()), "decode_attn: give text_src or text_shared, not both");
+  CHECK_IN((*t), torch::kInt32);
+  TORCH_CHECK(t->numel() == B && t->device() == kc.device(), "text_src: one int32 per batch row (", B, "), on the caches' device");
+  TORCH_CHECK(kc.numel() / 8 < (1L << 31), "text_src: the cache is too large for 32-bit 16-byte indices");
+  return t->data_ptr<int>();
+}
 
 void decode_attn_part_(Tensor part, Tensor cosT, Tensor sinT, double qscale, Tensor kc, Tensor vc, Tensor out, Tensor pos,
-                       int64_t T, int64_t S, int64_t H, int64_t K, int64_t pattern, c10::optional<Tensor> text_shared) {
+                       int64_t T, int64_t S, int64_t H, int64_t K, int64_t pattern, c10::optional<Tensor> text_shared,
+                       c10::optional<Tensor> text_src) {
   CHECK_IN(part, torch::kFloat32); CHECK_IN(cosT, torch::kFloat32); CHECK_IN(sinT, torch::kFloat32);
   CHECK_IN(kc, torch::kBFloat16); CHECK_IN(vc, torch::kBFloat16); CHECK_IN(out, torch::kBFloat16); CHECK_IN(pos, torch::kInt32);
   const int BH = kc.size(0), B = BH / H;
@@ -1207,7 +1219,7 @@ void decode_attn_part_(Tensor part, Tensor cosT, Tensor sinT, double qscale, Ten
   auto g = make_decode_geom(T, S, kc.size(1), H, K, pattern);
   dalle::decode_attn_part(part.data_ptr<float>(), part.size(0), cosT.data_ptr<float>(), sinT.data_ptr<float>(), (float)qscale,
                           kc.data_ptr(), vc.data_ptr(), out.data_ptr(), pos.data_ptr<int>(), g, B, cur_stream(),
-                          shared_flag(text_shared));
+                          shared_flag(text_shared), text_src_rows(text_src, text_shared, B, kc));
 }
 
 // caption prefill: qkv (B, P, 3*H*64) bf16 -> q (B*H, P, 64) rotated + pre-scaled, k / v rotated into cache rows 0..P-1
@@ -1268,7 +1280,7 @@ void decode_rope_(Tensor qkv, Tensor cosT, Tensor sinT, Tensor q, Tensor kc, Ten
 }
 
 void decode_attn_(Tensor q, Tensor kc, Tensor vc, Tensor out, Tensor pos, int64_t T, int64_t S, int64_t H, int64_t K,
-                  int64_t pattern, c10::optional<Tensor> text_shared) {
+                  int64_t pattern, c10::optional<Tensor> text_shared, c10::optional<Tensor> text_src) {
   CHECK_IN(q, torch::kBFloat16); CHECK_IN(kc, torch::kBFloat16); CHECK_IN(vc, torch::kBFloat16);
   CHECK_IN(out, torch::kBFloat16); CHECK_IN(pos, torch::kInt32);
   const int BH = kc.size(0);
@@ -1276,19 +1288,28 @@ void decode_attn_(Tensor q, Tensor kc, Tensor vc, Tensor out, Tensor pos, int64_
   TORCH_CHECK(kc.size(1) == T + S * S - 1, "decode cache must hold the full sequence");
   auto g = make_decode_geom(T, S, kc.size(1), H, K, pattern);
   dalle::decode_attn(q.data_ptr(), kc.data_ptr(), vc.data_ptr(), out.data_ptr(), pos.data_ptr<int>(), g, BH / H, cur_stream(),
-                     shared_flag(text_shared));
+                     shared_flag(text_shared), text_src_rows(text_src, text_shared, BH / H, kc));
 }
 
 // Fused sampler. Returns the raw samples (B,); with text/codes/tok given it also does the decode-step
 // bookkeeping at device position *pos (codes[:, pos - T + 1] = sample, tok = next input token).
 Tensor sample_step(Tensor logits, int64_t top_k, double top_p, double temperature, Tensor seed, Tensor pos,
                    c10::optional<Tensor> text, c10::optional<Tensor> codes, c10::optional<Tensor> tok, int64_t vt,
-                   c10::optional<Tensor> prime, c10::optional<Tensor> n_prime) {
+                   c10::optional<Tensor> prime, c10::optional<Tensor> n_prime, c10::optional<Tensor> cond_scale) {
   CHECK_IN(logits, torch::kFloat32); CHECK_IN(seed, torch::kInt64); CHECK_IN(pos, torch::kInt32);
   TORCH_CHECK(logits.dim() == 2 && logits.size(1) >= 1 && logits.size(1) <= 8192, "sample: logits must be (B, V <= 8192)");
   TORCH_CHECK(seed.numel() == 1 && pos.numel() == 1, "sample: seed / pos are device scalars");
   const int B = logits.size(0);
   dalle::SampleArgs a{};
+  // guided: rows [0, B / 2) conditional, [B / 2, B) unconditional; every (B, ...) operand below keeps all B rows
+  if (cond_scale.has_value()) {
+    TORCH_CHECK(cond_scale->is_cuda() && cond_scale->is_contiguous() && cond_scale->scalar_type() == torch::kFloat32 &&
+                    cond_scale->numel() == 1 && cond_scale->device() == logits.device(),
+                "sample: cond_scale must be one fp32 element on the logits' device");
+    TORCH_CHECK(B >= 2 && B % 2 == 0, "sample: guided logits hold an even number of rows (conditional; unconditional)");
+    a.cond_scale = cond_scale->data_ptr<float>();
+    a.b = B / 2;
+  }
   a.logits = logits.data_ptr<float>();
   a.B = B;
   a.V = logits.size(1);
@@ -1319,7 +1340,7 @@ Tensor sample_step(Tensor logits, int64_t top_k, double top_p, double temperatur
     a.prime = prime->data_ptr<int64_t>();
     a.n_prime = n_prime->data_ptr<int>();
   }
-  auto out = torch::empty({B}, logits.options().dtype(torch::kInt64));
+  auto out = torch::empty({a.cond_scale != nullptr ? a.b : B}, logits.options().dtype(torch::kInt64));  // guided: (b,)
   a.sampled = out.data_ptr<int64_t>();
   TORCH_CHECK(dalle::sample_step(a, cur_stream()), "sample: unsupported shape");
   return out;
@@ -1500,7 +1521,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("prefill_softmax_", &prefill_softmax_);
   m.def("prefill_residual_", &prefill_residual_);
   m.def("decode_attn_", &decode_attn_, py::arg("q"), py::arg("kc"), py::arg("vc"), py::arg("out"), py::arg("pos"), py::arg("T"),
-        py::arg("S"), py::arg("H"), py::arg("K"), py::arg("pattern"), py::arg("text_shared") = py::none());
+        py::arg("S"), py::arg("H"), py::arg("K"), py::arg("pattern"), py::arg("text_shared") = py::none(),
+        py::arg("text_src") = py::none());
   m.def("skinny_linear", &skinny_linear);
   m.def("skinny_partials", &skinny_partials);
   m.def("skinny_partials_ln_", &skinny_partials_ln_, py::arg("X"), py::arg("W"), py::arg("bias"), py::arg("scale"), py::arg("x"),
@@ -1510,7 +1532,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("residual_from_partials_", &residual_from_partials_, py::arg("x"), py::arg("part"), py::arg("pbias"), py::arg("pscale"));
   m.def("decode_attn_part_", &decode_attn_part_, py::arg("part"), py::arg("cosT"), py::arg("sinT"), py::arg("qscale"), py::arg("kc"),
         py::arg("vc"), py::arg("out"), py::arg("pos"), py::arg("T"), py::arg("S"), py::arg("H"), py::arg("K"), py::arg("pattern"),
-        py::arg("text_shared") = py::none());
+        py::arg("text_shared") = py::none(), py::arg("text_src") = py::none());
   m.def("skinny_force_config", &dalle::skinny_force_config);
   m.def("skinny_shape_info", &dalle::skinny_shape_info);
   m.def("skinny_geglu", &skinny_geglu);
@@ -1519,7 +1541,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("vq_embed", &vq_embed);
   m.def("sample_step", &sample_step, py::arg("logits"), py::arg("top_k"), py::arg("top_p"), py::arg("temperature"),
         py::arg("seed"), py::arg("pos"), py::arg("text") = py::none(), py::arg("codes") = py::none(),
-        py::arg("tok") = py::none(), py::arg("vt") = 0, py::arg("prime") = py::none(), py::arg("n_prime") = py::none());
+        py::arg("tok") = py::none(), py::arg("vt") = 0, py::arg("prime") = py::none(), py::arg("n_prime") = py::none(),
+        py::arg("cond_scale") = py::none());
   m.def("lamb_grad_norm", &lamb_grad_norm);
   m.def("lamb_step", &lamb_step);
 }

@@ -336,6 +336,10 @@ struct QkvPartials {
   // identical in every row's cache and all rows read them from row 0's (one L2-resident copy per head instead of
   // B copies streamed from HBM: the reference's generation workload repeats one query over the batch)
   const int* text_shared;
+  // per-row text source (may be null; not together with text_shared): (B,) batch rows, row b reads the text
+  // positions' K / V from row text_src[b]'s cache of the same head -- classifier-free guidance, where one half of
+  // the rows carries the null caption and the other half possibly one repeated caption. Clamped to [0, B).
+  const int* text_src;
 };
 
 __device__ __forceinline__ int decode_num_keys(const DecodeGeom& g, int pos, int& nloc, int& r0, int& c0, int& nr, int& nc) {
@@ -401,7 +405,7 @@ __device__ __forceinline__ float slot_sum(float v) {  // over the 8 lanes of one
   return v;
 }
 
-template <bool FROM_PART>
+template <bool FROM_PART, bool SRC>
 __global__ __launch_bounds__(256) void decode_attn_kernel(const __bf16* __restrict__ q, __bf16* __restrict__ kc,
                                                           __bf16* __restrict__ vc, __bf16* __restrict__ out,
                                                           const int* __restrict__ pos_ptr, DecodeGeom g, QkvPartials qp) {
@@ -413,6 +417,8 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(const __bf16* __restri
   const int bh = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int sub = lane & 7, slot = lane >> 3;
   const int pos = *pos_ptr;
+  int srow = 0;
+  if (SRC) srow = qp.text_src[bh / g.H];  // workgroup-uniform: one scalar load, issued with the position's
   if (pos < 0 || pos >= g.n) return;  // a replay past the cache end is a no-op, never an OOB write
   int nloc, r0 = 0, c0 = 0, nr = 0, nc = 1;
   const int nkeys = decode_num_keys(g, pos, nloc, r0, c0, nr, nc);
@@ -421,8 +427,16 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(const __bf16* __restri
   const __bf16* vb = vc + (size_t)bh * g.n * 64 + sub * 8;
   // shared caption: text keys before this position come from row 0 of the same head (< 2^31 elements back:
   // B <= 64, H <= 32, n <= 2048); the new key itself (a text query's last key) stays this row's own
-  const int tshift = (qp.text_shared != nullptr && *qp.text_shared) ? -(bh / g.H) * g.H * g.n * 64 : 0;
+  const int tshift = SRC ? 0 : (qp.text_shared != nullptr && *qp.text_shared) ? -(bh / g.H) * g.H * g.n * 64 : 0;
   const int tlim = min(g.T, pos);
+  // SRC: the same keys from row text_src[b]'s cache; the distance in 64 bits (B * H * n * 64 elements reach 2^33),
+  // the entry clamped to the batch so that a bad one reads a wrong row, never out of bounds
+  long sshift = 0;
+  if (SRC) sshift = ((long)min(max(srow, 0), (int)gridDim.x / g.H - 1) - bh / g.H) * g.H * g.n * 64;
+  auto src_off = [&](int i) -> long { return SRC && i < tlim ? sshift : 0L; };
+  // the single-chunk path keeps one 32-bit index per key as the other instantiation does: in 16-byte units (a
+  // lane's 8 dims), where the distance fits (host-checked: B * H * n * 8 < 2^31)
+  const int sshift8 = (int)(sshift >> 3);
 
   // FROM_PART: q / k / v of the new token are split-K slabs of the QKV projection (threads 0..95: q | k
   // | v x dim pair). Every load the query needs before its first score -- q, or its slabs and rotary
@@ -502,13 +516,16 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(const __bf16* __restri
 #pragma unroll
     for (int u = 0; u < DA_U; ++u) {
       const int i = min(u * 32 + wave * 8 + slot, nkeys - 1);
-      kidx[u] = decode_key_at(g, i, pos, r0, c0, nc) * 64 + (i < tlim ? tshift : 0);
+      kidx[u] = SRC ? decode_key_at(g, i, pos, r0, c0, nc) * 8 + (i < tlim ? sshift8 : 0)
+                    : decode_key_at(g, i, pos, r0, c0, nc) * 64 + (i < tlim ? tshift : 0);
     }
 #pragma unroll
-    for (int u = 0; u < DA_U; ++u) kf[u] = *reinterpret_cast<const s16x8*>(kb + kidx[u]);
+    for (int u = 0; u < DA_U; ++u)
+      kf[u] = SRC ? reinterpret_cast<const s16x8*>(kb)[kidx[u]] : *reinterpret_cast<const s16x8*>(kb + kidx[u]);
     asm volatile("" ::: "memory");  // every K row ahead of every V row: the scores start while V streams
 #pragma unroll
-    for (int u = 0; u < DA_U; ++u) vf[u] = *reinterpret_cast<const s16x8*>(vb + kidx[u]);
+    for (int u = 0; u < DA_U; ++u)
+      vf[u] = SRC ? reinterpret_cast<const s16x8*>(vb)[kidx[u]] : *reinterpret_cast<const s16x8*>(vb + kidx[u]);
     prologue();
     if (FROM_PART) {  // the new key is the last of the key list
       const s16x8 kn = *reinterpret_cast<const s16x8*>(&kvsh[0][sub * 8]);
@@ -564,7 +581,7 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(const __bf16* __restri
 #pragma unroll
       for (int u = 0; u < DA_U; ++u) {
         const int i = c + u * 32 + wave * 8 + slot;
-        kf[u] = i < nkeys ? *reinterpret_cast<const s16x8*>(kb + ((long)decode_key_at(g, i, pos, r0, c0, nc) * 64 + (i < tlim ? tshift : 0)))
+        kf[u] = i < nkeys ? *reinterpret_cast<const s16x8*>(kb + ((long)decode_key_at(g, i, pos, r0, c0, nc) * 64 + (i < tlim ? tshift : 0) + src_off(i)))
                           : s16x8{};
       }
 #pragma unroll
@@ -587,7 +604,7 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(const __bf16* __restri
 #pragma unroll
       for (int u = 0; u < DA_U; ++u) {
         const int i = c + u * 32 + wave * 8 + slot;
-        vf[u] = i < nkeys ? *reinterpret_cast<const s16x8*>(vb + ((long)decode_key_at(g, i, pos, r0, c0, nc) * 64 + (i < tlim ? tshift : 0)))
+        vf[u] = i < nkeys ? *reinterpret_cast<const s16x8*>(vb + ((long)decode_key_at(g, i, pos, r0, c0, nc) * 64 + (i < tlim ? tshift : 0) + src_off(i)))
                           : s16x8{};
       }
 #pragma unroll
@@ -664,17 +681,27 @@ void decode_rope(const void* qkv, const float* cosT, const float* sinT, void* q,
 }
 
 void decode_attn(const void* q, void* kc, void* vc, void* out, const int* pos, const DecodeGeom& g, int B, hipStream_t st,
-                 const int* text_shared) {
+                 const int* text_shared, const int* text_src) {
   QkvPartials qp{};
   qp.text_shared = text_shared;
-  hipLaunchKernelGGL(decode_attn_kernel<false>, dim3(B * g.H), dim3(256), 0, st, (const __bf16*)q, (__bf16*)kc, (__bf16*)vc,
-                     (__bf16*)out, pos, g, qp);
+  qp.text_src = text_src;
+  if (text_src != nullptr)
+    hipLaunchKernelGGL((decode_attn_kernel<false, true>), dim3(B * g.H), dim3(256), 0, st, (const __bf16*)q, (__bf16*)kc,
+                       (__bf16*)vc, (__bf16*)out, pos, g, qp);
+  else
+    hipLaunchKernelGGL((decode_attn_kernel<false, false>), dim3(B * g.H), dim3(256), 0, st, (const __bf16*)q, (__bf16*)kc,
+                       (__bf16*)vc, (__bf16*)out, pos, g, qp);
 }
 
 void decode_attn_part(const float* part, int KS, const float* cosT, const float* sinT, float qscale, void* kc, void* vc, void* out,
-                      const int* pos, const DecodeGeom& g, int B, hipStream_t st, const int* text_shared) {
-  hipLaunchKernelGGL(decode_attn_kernel<true>, dim3(B * g.H), dim3(256), 0, st, (const __bf16*)nullptr, (__bf16*)kc, (__bf16*)vc,
-                     (__bf16*)out, pos, g, QkvPartials{part, cosT, sinT, KS, B, qscale, text_shared});
+                      const int* pos, const DecodeGeom& g, int B, hipStream_t st, const int* text_shared, const int* text_src) {
+  const QkvPartials qp{part, cosT, sinT, KS, B, qscale, text_shared, text_src};
+  if (text_src != nullptr)
+    hipLaunchKernelGGL((decode_attn_kernel<true, true>), dim3(B * g.H), dim3(256), 0, st, (const __bf16*)nullptr, (__bf16*)kc,
+                       (__bf16*)vc, (__bf16*)out, pos, g, qp);
+  else
+    hipLaunchKernelGGL((decode_attn_kernel<true, false>), dim3(B * g.H), dim3(256), 0, st, (const __bf16*)nullptr, (__bf16*)kc,
+                       (__bf16*)vc, (__bf16*)out, pos, g, qp);
 }
 
 void vq_embed(const int64_t* idx, const float* codebook, float* z, int HW, int C, int B, hipStream_t st) {

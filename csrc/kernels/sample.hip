@@ -17,6 +17,11 @@
 // token during prefill, else the sample shifted into the image vocabulary). With a `prime` table the first
 // *n_prime image positions take the table's code in place of the sample (image-primed generation; the count is
 // a device scalar, so one captured graph serves every prefix length).
+// Guided (classifier-free guidance, `cond_scale` given): the logits are (2 b, V), conditional rows on top of the
+// unconditional ones; workgroup r of b forms m = u + s * (c - u) from rows r and r + b in three separately rounded
+// fp32 operations while loading, samples from m exactly as above (noise keyed by r) and writes the code and the next
+// input token of BOTH rows. The scale is a device scalar: one captured graph serves every scale. A second
+// instantiation of the kernel, so the unguided one keeps its code.
 #include "common.h"
 #include "geom.h"
 
@@ -76,6 +81,7 @@ __device__ __forceinline__ int wave_sum_int(int v) {
   return v;
 }
 
+template <bool GUIDED>
 __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(SampleArgs a) {
   __shared__ uint64_t srt[SMP_VMAX];  // top-p: (key << 32 | ~index), 64 KB
   __shared__ int cntb[2][SMP_NW];
@@ -85,7 +91,22 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(SampleArgs a) {
   const float* lr = a.logits + (size_t)row * a.V;
 
   uint32_t key[SMP_VPT];
-  {
+  if (GUIDED) {
+    // both rows' (clamped) loads in flight together, then the mix: sub, mul, add each rounded on its own (no fma
+    // contraction), so the result is bitwise the host's u + s * (c - u) in fp32
+    const float* ur = a.logits + (size_t)(row + a.b) * a.V;
+    const float s = *a.cond_scale;
+    float lc[SMP_VPT], lu[SMP_VPT];
+#pragma unroll
+    for (int i = 0; i < SMP_VPT; ++i) lc[i] = lr[min(i * SMP_THREADS + tid, a.V - 1)];
+#pragma unroll
+    for (int i = 0; i < SMP_VPT; ++i) lu[i] = ur[min(i * SMP_THREADS + tid, a.V - 1)];
+#pragma unroll
+    for (int i = 0; i < SMP_VPT; ++i) {
+      const float m = __fadd_rn(lu[i], __fmul_rn(s, __fsub_rn(lc[i], lu[i])));
+      key[i] = i * SMP_THREADS + tid < a.V ? order_key(m) : 0u;
+    }
+  } else {
     // unconditional (clamped) loads: all 32 in flight at once (a guarded load per slot compiled to 32 serial
     // load -> vmcnt(0) round trips, ~7 us per row)
     float lv[SMP_VPT];
@@ -241,12 +262,27 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(SampleArgs a) {
     if (a.tok) {
       a.tok[row] = (pos + 1 < a.T) ? a.text[(size_t)row * a.T + min(pos + 1, a.T - 1)] : nxt + a.vt;
     }
+    if (GUIDED) {  // the unconditional row takes the same code; during the caption its own next caption id
+      const int ru = row + a.b;
+      if (a.codes) {
+        const int ci = min(max(pos - (a.T - 1), 0), a.img_len - 1);
+        a.codes[(size_t)ru * a.img_len + ci] = nxt;
+      }
+      if (a.tok) {
+        a.tok[ru] = (pos + 1 < a.T) ? a.text[(size_t)ru * a.T + min(pos + 1, a.T - 1)] : nxt + a.vt;
+      }
+    }
   }
 }
 
 bool sample_step(const SampleArgs& a, hipStream_t st) {
   if (a.B < 1 || a.V < 1 || a.V > SMP_VMAX) return false;
-  hipLaunchKernelGGL(sample_kernel, dim3(a.B), dim3(SMP_THREADS), 0, st, a);
+  if (a.cond_scale != nullptr) {
+    if (a.b < 1 || a.B != 2 * a.b) return false;
+    hipLaunchKernelGGL(sample_kernel<true>, dim3(a.b), dim3(SMP_THREADS), 0, st, a);
+    return true;
+  }
+  hipLaunchKernelGGL(sample_kernel<false>, dim3(a.B), dim3(SMP_THREADS), 0, st, a);
   return true;
 }
 

@@ -265,8 +265,17 @@ class DALLE(nn.Module):
             tokens = tokens[:, :-1]
         return tokens
 
-    def forward(self, text, image=None, mask=None, return_loss: bool = False):
-        """``mask`` is accepted for API parity and ignored, as in the pinned fork."""
+    def forward(self, text, image=None, mask=None, return_loss: bool = False, null_cond_prob: float = 0.0, generator=None):
+        """``mask`` is accepted for API parity and ignored, as in the pinned fork.
+
+        ``null_cond_prob``: classifier-free guidance training (dalle-pytorch's rule): with this probability per sample
+        the caption ids become 0, the pad id, which the pad remap turns into the null caption. 0 draws no random
+        numbers; ``generator`` seeds the draw."""
+        if not 0.0 <= null_cond_prob <= 1.0:
+            raise ValueError(f"null_cond_prob must be in [0, 1], got {null_cond_prob}")
+        if null_cond_prob > 0:
+            drop = torch.rand(text.shape[0], device=text.device, generator=generator) < null_cond_prob
+            text = text * (~drop).to(text.dtype)[:, None]
         text_bos = self.prepare_text(text)
         if image is not None and image.dim() == 4:
             assert self.vae is not None, "raw images need a VAE"
@@ -295,16 +304,23 @@ class DALLE(nn.Module):
     @torch.no_grad()
     def generate_images(self, text, *, clip=None, mask=None, filter_thres=None, temperature: float = 1.0, img=None,
                         num_init_img_tokens=None, top_k: int = 0, top_p: float = 1.0, use_cache: bool = True,
-                        return_codes: bool = False, use_graph=None):
+                        return_codes: bool = False, use_graph=None, cond_scale: float = 1.0):
         """Sample 1024 image tokens per caption with the KV-cache decoder (hipGraph-replayed on MI355X)
         and decode them with ``self.vae`` to (b, 3, H, W) images in [0, 1] (codes if no VAE).
 
         ``img`` primes the generation (dalle-pytorch's image completion / variations): a (b, 3, S, S) float
         picture in [0, 1] is encoded with ``self.vae.get_codebook_indices``; a 2-D integer tensor is taken as image
         codes (works without a VAE). Its first ``num_init_img_tokens`` codes (default ``int(0.4375 *
-        image_seq_len)``, as dalle-pytorch) are forced as the first image tokens and the rest is sampled."""
+        image_seq_len)``, as dalle-pytorch) are forced as the first image tokens and the rest is sampled.
+
+        ``cond_scale``: classifier-free guidance (for a model trained with ``null_cond_prob``). 1 is the plain path;
+        any other value runs every picture's caption and the null caption side by side and samples from
+        ``null + (cond - null) * cond_scale``, on a guided engine cached beside the plain one."""
         from .generation import make_decode_engine
 
+        if cond_scale < 0:
+            raise ValueError(f"cond_scale must be >= 0, got {cond_scale}")
+        guided = cond_scale != 1
         if filter_thres is not None and not top_k:
             top_k = max(1, int((1 - filter_thres) * self.num_image_tokens))
         text_bos = self.prepare_text(text)
@@ -324,11 +340,14 @@ class DALLE(nn.Module):
             if img.shape[1] < k:
                 raise ValueError(f"img holds {img.shape[1]} codes, fewer than the {k} to prime with")
             prime = img[:, :k].long().to(text.device)
-        eng = getattr(self, "_decode_engine", None)
+        slot = "_guided_decode_engine" if guided else "_decode_engine"
+        eng = getattr(self, slot, None)
         if eng is None or eng.B != text.shape[0] or eng.device != text.device:
-            eng = make_decode_engine(self, text.shape[0], device=text.device)
-            self._decode_engine = eng
+            eng = make_decode_engine(self, text.shape[0], device=text.device, **({"guided": True} if guided else {}))
+            setattr(self, slot, eng)
         kw = {} if prime is None else {"prime": prime}
+        if guided:
+            kw["cond_scale"] = float(cond_scale)
         codes = eng.generate(text_bos, temperature=temperature, top_k=top_k, top_p=top_p, use_graph=use_graph, **kw)
         if return_codes or self.vae is None:
             return codes

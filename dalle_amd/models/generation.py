@@ -49,8 +49,11 @@ def gumbel_sample(logits: torch.Tensor, temperature: float = 1.0, generator=None
 
 class DecodeEngine:
     def __init__(self, model, batch_size: int, device=None, use_hip: Optional[bool] = None, skinny: bool = True,
-                 partials: int = 2, fused_sampler: bool = True, ln_tail: Optional[bool] = None):
-        """``skinny``: decode projections on the skinny MFMA GEMM with fused epilogues (when the shapes allow);
+                 partials: int = 2, fused_sampler: bool = True, ln_tail: Optional[bool] = None, guided: bool = False):
+        """``guided``: classifier-free guidance. The engine then owns ``2 * batch_size`` rows -- the pictures' captions
+        on top, the null caption below -- and samples picture ``r`` from ``u + cond_scale * (c - u)`` of rows ``r`` /
+        ``r + batch_size`` (in the fused sampler's one launch), feeding the chosen code back to both rows.
+        ``skinny``: decode projections on the skinny MFMA GEMM with fused epilogues (when the shapes allow);
         ``partials``: 2 = every projection leaves split-K slabs summed by its consumer (measured fastest,
         profiles/r2_decode_partials_ab.txt), 1 = the residual projections only, 0 = in-GEMM split-K hand-off;
         ``fused_sampler``: the one-kernel top-k / top-p / Gumbel sampler (K18); ``ln_tail`` (None: env
@@ -62,7 +65,9 @@ class DecodeEngine:
         The non-default forms are kept for the numerics A/B in tests/test_generation_gpu.py."""
         self.model = model
         cfg = self.cfg = model.cfg
-        self.B = batch_size
+        self.B = batch_size  # pictures, as callers see it; R rows of caches, histories and buffers
+        self.guided = bool(guided)
+        self.R = 2 * batch_size if self.guided else batch_size
         self.device = device or next(model.parameters()).device
         dev = self.device
         if use_hip is None:
@@ -76,7 +81,7 @@ class DecodeEngine:
         tr = model.transformer
         self.pairs = tr.layers.pairs()
         self.geom = tr.geom
-        L, B = len(self.pairs), batch_size
+        L, B = len(self.pairs), self.R
         self.kc = [torch.zeros(B * self.H, self.n, self.Dh, dtype=self.cdt, device=dev) for _ in range(L)]
         self.vc = [torch.zeros_like(k) for k in self.kc]
         self.hist = [[torch.zeros(B, self.n, self.d, dtype=self.cdt, device=dev) for _ in range(2)] for _ in range(L)]
@@ -86,6 +91,14 @@ class DecodeEngine:
         # cases): the decode attention then reads the text positions' K / V from row 0's cache for all rows
         self.text_shared = torch.zeros(1, dtype=torch.int32, device=dev)
         self.share_text = True
+        # guided: the per-row form of the same saving. Row r reads the text positions' K / V from row text_src[r]'s
+        # cache: the null rows from the first null row, the caption rows from row 0 when all captions are equal,
+        # else from themselves (filled per generate call, on device). ``share_src`` = False: every row its own.
+        # An engine with ``text_src`` set passes it to the decode attention in place of ``text_shared``.
+        self.text_src = torch.arange(B, dtype=torch.int32, device=dev) if self.guided else None
+        self.share_src = True
+        self.cond_scale = torch.ones(1, dtype=torch.float32, device=dev) if self.guided else None
+        self._null_text = None
         self.tok = torch.zeros(B, dtype=torch.long, device=dev)
         self.hbuf = torch.zeros(B, self.d, dtype=self.cdt, device=dev)
         self.qbuf = torch.zeros(B, self.H, self.Dh, dtype=self.cdt, device=dev)
@@ -106,7 +119,7 @@ class DecodeEngine:
         self._w = {}
         # decode-step projections through the skinny MFMA GEMM (csrc/kernels/skinny.hip) with the
         # rotary / GEGLU / LayerScale-residual epilogues fused: M = batch <= 64 rows
-        self.skinny = (use_hip and skinny and batch_size <= 64 and self.d % 128 == 0 and (cfg.ff_mult * self.d) % 128 == 0)
+        self.skinny = (use_hip and skinny and B <= 64 and self.d % 128 == 0 and (cfg.ff_mult * self.d) % 128 == 0)
         self.sk_cnt = torch.zeros(8192, dtype=torch.int32, device=dev) if self.skinny else None
         # split-K partials: the projections leave fp32 slabs summed by their consumer, so those GEMMs
         # split K over 4-8x the workgroups with no cross-workgroup hand-off. 2 (default): out-proj /
@@ -216,12 +229,12 @@ class DecodeEngine:
         if self.qkv_partials:
             part = C().skinny_partials(h, self._wt(attn.to_qkv.weight))
             C().decode_attn_part_(part, self.cos, self.sin, self.Dh ** -0.5, self.kc[li], self.vc[li], self.obuf, self.pos,
-                                  self.T, self.S, self.H, self.geom.kernel_size, PATTERN_IDS[attn.attn_type], self.text_shared)
+                                  self.T, self.S, self.H, self.geom.kernel_size, PATTERN_IDS[attn.attn_type], **self._text_kw())
         else:
             C().skinny_qkv_rope_(h, self._wt(attn.to_qkv.weight), self.cos, self.sin, self.qbuf, self.kc[li], self.vc[li],
                                  self.pos, self.H, self.Dh ** -0.5, self.sk_cnt)
             C().decode_attn_(self.qbuf, self.kc[li], self.vc[li], self.obuf, self.pos, self.T, self.S, self.H,
-                             self.geom.kernel_size, PATTERN_IDS[attn.attn_type], self.text_shared)
+                             self.geom.kernel_size, PATTERN_IDS[attn.attn_type], **self._text_kw())
         if self.ln_tail:
             self._pending = ("gemm", x_res, self.obuf, self._wt(attn.to_out[0].weight), self._wt(attn.to_out[0].bias),
                              self._scale(ls))
@@ -252,6 +265,10 @@ class DecodeEngine:
         C().skinny_residual_(x_res, a, self._wt(ff.net[3].weight), self._wt(ff.net[3].bias), self._scale(ls), self.sk_cnt)
         return x_res
 
+    def _text_kw(self):
+        """Where the decode attention reads the text positions' K / V: the all-rows flag, or the per-row sources."""
+        return {"text_shared": self.text_shared} if self.text_src is None else {"text_src": self.text_src}
+
     def _scale(self, ls):
         ent = self._w.get(("scale", id(ls.scale)))
         if ent is None:
@@ -268,7 +285,7 @@ class DecodeEngine:
             C().decode_rope_(qkv.contiguous(), self.cos, self.sin, self.qbuf, self.kc[li], self.vc[li], self.pos, self.H,
                              self.Dh ** -0.5)
             C().decode_attn_(self.qbuf, self.kc[li], self.vc[li], self.obuf, self.pos, self.T, self.S, self.H,
-                             self.geom.kernel_size, PATTERN_IDS[attn.attn_type], self.text_shared)
+                             self.geom.kernel_size, PATTERN_IDS[attn.attn_type], **self._text_kw())
             o = self.obuf
         else:
             o = self._attn_torch(li, attn, qkv)
@@ -278,7 +295,7 @@ class DecodeEngine:
         from ..ops.reference import split_heads
         from .rotary import apply_rotary
         p = int(self.pos)
-        B, H, Dh = self.B, self.H, self.Dh
+        B, H, Dh = self.R, self.H, self.Dh
         q, k, v = (t.view(B, H, 1, Dh) for t in qkv.chunk(3, dim=-1))
         c, s = self.cos[p:p + 1], self.sin[p:p + 1]
         q, k, v = (apply_rotary(t, c, s) for t in (q, k, v))
@@ -349,17 +366,24 @@ class DecodeEngine:
             from ..ops.hip_ops import C
             C().sample_step(logits, int(self.top_k or 0), float(1.0 if self.top_p is None else self.top_p),
                             float(self.temperature), self.seed, self.pos, self.text_bos, self.codes, self.tok, self.Vt,
-                            prime=self.prime, n_prime=self.n_prime)
+                            prime=self.prime, n_prime=self.n_prime, **({"cond_scale": self.cond_scale} if self.guided else {}))
             self.pos.add_(1)
             return logits
+        B, R = self.B, self.R
+        if self.guided:  # the sampler's mix: three separately rounded fp32 operations
+            c, u = logits[:B].float(), logits[B:].float()
+            logits = u + self.cond_scale * (c - u)
         logits = filter_logits(logits, self.top_k, self.top_p)
         nxt = gumbel_sample(logits, self.temperature)
         p = self.pos.long()
         ci = p - (self.T - 1)
-        idx = ci.clamp(0, self.cfg.image_seq_len - 1).view(1, 1).expand(self.B, 1)
-        nxt = torch.where((ci >= 0) & (ci < self.n_prime), self.prime.gather(1, idx).view(self.B), nxt)
-        self.codes.scatter_(1, idx, nxt.view(self.B, 1))
-        nxt_text = self.text_bos.gather(1, (p + 1).clamp(max=self.T - 1).view(1, 1).expand(self.B, 1)).view(self.B)
+        idx = ci.clamp(0, self.cfg.image_seq_len - 1).view(1, 1).expand(B, 1)
+        nxt = torch.where((ci >= 0) & (ci < self.n_prime), self.prime[:B].gather(1, idx).view(B), nxt)
+        if self.guided:  # both halves take the picture's code
+            nxt = torch.cat([nxt, nxt])
+            idx = idx.repeat(2, 1)
+        self.codes.scatter_(1, idx, nxt.view(R, 1))
+        nxt_text = self.text_bos.gather(1, (p + 1).clamp(max=self.T - 1).view(1, 1).expand(R, 1)).view(R)
         self.tok.copy_(torch.where(p + 1 < self.T, nxt_text, nxt + self.Vt))
         self.pos.add_(1)
         return logits
@@ -367,13 +391,34 @@ class DecodeEngine:
     _image_step = _step
 
     # -- public API ---------------------------------------------------------------------------------
+    def _rows_text(self, text_bos: torch.Tensor) -> torch.Tensor:
+        """The caption table of all rows: a guided engine puts the null caption (``prepare_text`` of pad ids) under
+        the caller's (B, T) captions; a table that already holds 2 B rows passes."""
+        if not self.guided or text_bos.shape[0] == self.R:
+            return text_bos
+        if self._null_text is None:
+            zeros = torch.zeros(1, self.cfg.text_seq_len, dtype=text_bos.dtype, device=text_bos.device)
+            self._null_text = self.model.prepare_text(zeros)
+        return torch.cat([text_bos, self._null_text.to(text_bos.dtype).expand(self.B, -1)])
+
     def _start(self, text_bos: torch.Tensor):
         self.reset()
+        text_bos = self._rows_text(text_bos)
         if not hasattr(self, "text_bos") or self.text_bos.shape != text_bos.shape:
             self.text_bos = torch.zeros_like(text_bos)
         self.text_bos.copy_(text_bos)
         self.tok.copy_(text_bos[:, 0])
-        if self.share_text:
+        if self.guided:
+            # text_shared: all CAPTION rows equal (the null rows always are). Sources: caption rows -> row 0 if so,
+            # else themselves; null rows -> the first null row
+            B = self.B
+            self.text_shared.copy_((text_bos[:B] == text_bos[:1]).all().view(1))
+            if self.share_src:
+                self.text_src[:B].copy_(torch.arange(B, dtype=torch.int32, device=self.device) * (1 - self.text_shared))
+                self.text_src[B:].fill_(B)
+            else:
+                self.text_src.copy_(torch.arange(self.R, dtype=torch.int32, device=self.device))
+        elif self.share_text:
             self.text_shared.copy_((text_bos == text_bos[:1]).all().view(1))
         else:
             self.text_shared.zero_()
@@ -385,19 +430,20 @@ class DecodeEngine:
             self.n_prime.zero_()
             return
         L = self.cfg.image_seq_len
-        if prime.dim() != 2 or prime.shape[0] != self.B or not 0 <= prime.shape[1] < L:
+        if prime.dim() != 2 or prime.shape[0] != self.B or not 0 <= prime.shape[1] < L:  # B pictures: the sampler reads rows [0, B)
             raise ValueError(f"prime must be (batch {self.B}, k) with 0 <= k < {L}, got {tuple(prime.shape)}")
         if prime.dtype.is_floating_point or prime.dtype == torch.bool:
             raise ValueError("prime must hold integer image codes")
         k = prime.shape[1]
         if k:
-            self.prime[:, :k].copy_(prime)
+            self.prime[:self.B, :k].copy_(prime)
         self.n_prime.fill_(k)
 
     @torch.no_grad()
     def prefill(self, text_bos: torch.Tensor):
         """Eagerly feed BOS + text positions 0..T-2 (position T-1 is the first sampling step)."""
         self._start(text_bos)
+        text_bos = self.text_bos  # all rows' captions (a guided engine added the null rows)
         for p in range(self.T - 1):
             self.tok.copy_(text_bos[:, p])
             self._forward_position()
@@ -507,6 +553,12 @@ class DecodeEngine:
     def _pf_rows(self) -> int:
         """Rows the caption prefill runs for (after ``_start``): 1 when every row holds row 0's caption (a
         host read of the device flag: the one synchronisation of the prefill), else the batch."""
+        if self.guided:
+            # all rows, whatever the sources (no host read): the prefill's library GEMMs pick their algorithm by
+            # the row count, so a pass over the source rows' prefix [0, B] rounds differently from the full pass
+            # and guided sampling would depend, in the last bit, on whether the text reads are shared. The pass is
+            # under 2 % of a call; the saving of sharing is in the 1024 decode steps' reads
+            return self.R
         one = self.use_hip and self.share_text and self.B > 1 and bool(self.text_shared.item())
         return 1 if one else self.B
 
@@ -543,7 +595,7 @@ class DecodeEngine:
             else:
                 self._pf_body(rows, P)
             self.pos.fill_(P)
-        self.tok.copy_(text_bos[:, P])
+        self.tok.copy_(self.text_bos[:, P])
 
     def _pf_body(self, rows: int, P: int):
         W = self.model.to_logits[1].weight.detach()
@@ -557,7 +609,7 @@ class DecodeEngine:
             for li, (f, g) in enumerate(self.pairs):
                 x = self._pf_add(x, f, self._pf_attn(li, f, x))
                 x = self._pf_add(x, g, self._pf_ff(li, g, x))
-        if rows < self.B:  # the other rows' own reads: the LN history the first decode step shifts in
+        if rows < self.R:  # the other rows' own reads: the LN history the first decode step shifts in
             for hs in self.hist:
                 for hb in hs:
                     hb[rows:, P - 1].copy_(hb[0, P - 1].expand(self.B - rows, -1))
@@ -565,13 +617,22 @@ class DecodeEngine:
     @torch.no_grad()
     def generate(self, text_bos: torch.Tensor, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
                  use_graph: Optional[bool] = None, seed: Optional[int] = None, parallel_prefill: Optional[bool] = None,
-                 prime: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 prime: Optional[torch.Tensor] = None, cond_scale: Optional[float] = None) -> torch.Tensor:
         """The caption prefill (one batched pass per layer, ``parallel_prefill``, default on; else T-1
         decode steps) then the 1024 sampled image tokens through one step function; on MI355X that step
         is a single hipGraph replayed per position. ``seed`` fixes the fused sampler's noise (default:
         drawn from torch's global generator). ``prime`` (B, k) image codes: the first ``k`` image tokens are
         forced to them (ordinary decode steps whose sample is replaced) and the rest sampled; the noise stays a
-        function of (seed, position, row, token), so positions >= k draw what an unprimed call draws there."""
+        function of (seed, position, row, token), so positions >= k draw what an unprimed call draws there.
+        ``cond_scale`` (guided engines only): the guidance scale, a device scalar the captured step reads -- another
+        scale replays the same graph; 1 samples from the conditional rows' logits, 0 from the null caption's."""
+        if cond_scale is not None and not self.guided:
+            raise ValueError("cond_scale needs an engine built with guided=True")
+        if self.guided:
+            s = 1.0 if cond_scale is None else float(cond_scale)
+            if s < 0:
+                raise ValueError(f"cond_scale must be >= 0, got {s}")
+            self.cond_scale.fill_(s)
         self.temperature, self.top_k, self.top_p = temperature, top_k, top_p
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
@@ -594,7 +655,7 @@ class DecodeEngine:
                 self.graph.replay()
             else:
                 self._step()
-        return self.codes.clone()
+        return self.codes[:self.B].clone()
 
     def _capture(self):
         """Capture one image step into a hipGraph (warm-up on a side stream as torch requires)."""
@@ -618,6 +679,8 @@ class DecodeEngine:
     def teacher_forced_logits(self, text_bos: torch.Tensor, image: torch.Tensor) -> torch.Tensor:
         """Image-vocab logits at every position >= T-1 when feeding the given image codes (tests)."""
         self.prefill(text_bos)
+        if image.shape[0] != self.R:  # guided: both halves are fed the pictures' codes
+            image = image.repeat(self.R // image.shape[0], 1)
         outs = []
         for i in range(self.cfg.image_seq_len):
             outs.append(self._forward_position())
@@ -653,11 +716,15 @@ class SplitDecodeEngine:
     node by node, ~2.5 ms of host time per ~3 ms step, so the host barely stays ahead and its jitter reaches
     the GPU (profiles/r6_decode_replay_host.txt: 3.00-3.02 vs 3.05-3.11 ms per step)."""
 
-    def __init__(self, model, batch_size: int, device=None, parts: int = 2, graphs: Optional[str] = None):
+    def __init__(self, model, batch_size: int, device=None, parts: int = 2, graphs: Optional[str] = None,
+                 guided: bool = False):
+        """``guided``: every part is a guided engine over its slice of the pictures, with its own conditional and
+        null rows, so no part reads another's buffers."""
         if batch_size % parts:
             raise ValueError(f"batch {batch_size} is not divisible into {parts} parts")
         self.model, self.B, self.nparts = model, batch_size, parts
-        self.parts = [DecodeEngine(model, batch_size // parts, device=device) for _ in range(parts)]
+        self.guided = bool(guided)
+        self.parts = [DecodeEngine(model, batch_size // parts, device=device, guided=guided) for _ in range(parts)]
         for p in self.parts[1:]:
             p._w = self.parts[0]._w  # one bf16 copy of every weight, refreshed by part 0 only
             p._refresh_weights = False
@@ -674,7 +741,7 @@ class SplitDecodeEngine:
 
     @property
     def codes(self) -> torch.Tensor:
-        return torch.cat([p.codes for p in self.parts])
+        return torch.cat([p.codes[:p.B] for p in self.parts])
 
     def _start_all(self, text_bos: torch.Tensor):
         b = self.B // self.nparts
@@ -760,9 +827,17 @@ class SplitDecodeEngine:
     @torch.no_grad()
     def generate(self, text_bos: torch.Tensor, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
                  use_graph: Optional[bool] = None, seed: Optional[int] = None,
-                 prime: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 prime: Optional[torch.Tensor] = None, cond_scale: Optional[float] = None) -> torch.Tensor:
         if prime is not None and (prime.dim() != 2 or prime.shape[0] != self.B):
             raise ValueError(f"prime must be (batch {self.B}, k), got {tuple(prime.shape)}")
+        if cond_scale is not None and not self.guided:
+            raise ValueError("cond_scale needs an engine built with guided=True")
+        if self.guided:
+            s = 1.0 if cond_scale is None else float(cond_scale)
+            if s < 0:
+                raise ValueError(f"cond_scale must be >= 0, got {s}")
+            for p in self.parts:
+                p.cond_scale.fill_(s)
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         for i, p in enumerate(self.parts):
@@ -819,11 +894,13 @@ def decode_parts(batch_size: int, device, parts: Optional[int] = None) -> int:
     return n if batch_size % n == 0 else 1
 
 
-def make_decode_engine(model, batch_size: int, device=None):
+def make_decode_engine(model, batch_size: int, device=None, guided: bool = False):
+    """``guided``: an engine for classifier-free guidance (two rows per picture). The split into parts is decided
+    on the row count; the skinny GEMM limit is 64 rows, so at most 32 guided pictures stay on that path."""
     device = device or next(model.parameters()).device
-    parts = decode_parts(batch_size, device)
-    if parts > 1:
-        eng = SplitDecodeEngine(model, batch_size, device=device, parts=parts)
+    parts = decode_parts(2 * batch_size if guided else batch_size, device)
+    if parts > 1 and batch_size % parts == 0:
+        eng = SplitDecodeEngine(model, batch_size, device=device, parts=parts, guided=guided)
         if eng.use_hip:
             return eng
-    return DecodeEngine(model, batch_size, device=device)
+    return DecodeEngine(model, batch_size, device=device, guided=guided)

@@ -80,8 +80,9 @@ def load_init_image(path: str, image_size: int) -> torch.Tensor:
 
 
 def generate(query, *, tokenizer, model, batch_size, n_iters, temperature, top_k, top_p, text_seq_len=256, device="cuda",
-             init_image=None, num_init_img_tokens=None):
-    """``init_image``: a (3, S, S) picture in [0, 1] (repeated over the batch) or (b, ...) images / codes, whose first
+             init_image=None, num_init_img_tokens=None, cond_scale=1.0):
+    """``cond_scale``: classifier-free guidance scale (``DALLE.generate_images(cond_scale=...)``; 1 = off).
+    ``init_image``: a (3, S, S) picture in [0, 1] (repeated over the batch) or (b, ...) images / codes, whose first
     ``num_init_img_tokens`` VQGAN codes every sample starts from (``DALLE.generate_images(img=...)``)."""
     ids = tokenizer(query, add_special_tokens=False, max_length=text_seq_len, truncation=True)['input_ids']
     input_ids = torch.full((text_seq_len,), 1, dtype=torch.long)
@@ -92,6 +93,8 @@ def generate(query, *, tokenizer, model, batch_size, n_iters, temperature, top_k
         if init_image.dim() == 3:
             init_image = init_image.unsqueeze(0).repeat(batch_size, 1, 1, 1)
         prime = dict(img=init_image.to(device), num_init_img_tokens=num_init_img_tokens)
+    if cond_scale != 1.0:
+        prime["cond_scale"] = cond_scale
     result = []
     for _ in range(n_iters):
         output = model.model.generate_images(input_ids, temperature=temperature, top_k=top_k, top_p=top_p, use_cache=True,
@@ -177,6 +180,8 @@ def main(argv=None):
                         help='[new] picture whose first VQGAN codes every sample starts from (image completion / variations)')
     parser.add_argument('--num-init-img-tokens', type=int, default=None,
                         help='[new] how many codes of --init-image to keep (default: 0.4375 of the image tokens)')
+    parser.add_argument('--cond-scale', type=float, default=1.0,
+                        help='[new] classifier-free guidance scale (1 = off; for models trained with --null_cond_prob)')
     args = parser.parse_args(argv)
     torch.set_grad_enabled(False)  # inference only (the reference disabled grads at import time)
 
@@ -222,7 +227,7 @@ def main(argv=None):
         images = generate(query, tokenizer=tokenizer, model=model, batch_size=args.batch_size, n_iters=args.n_iters,
                           temperature=args.temperature, top_k=args.top_k, top_p=args.top_p,
                           text_seq_len=model.model.text_seq_len, device=device, init_image=init_image,
-                          num_init_img_tokens=args.num_init_img_tokens)
+                          num_init_img_tokens=args.num_init_img_tokens, cond_scale=args.cond_scale)
         if clip_model is not None:
             from dalle_amd.models.clip import clip_scores as score_images
 

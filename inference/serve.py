@@ -6,16 +6,18 @@ each request goes to the device with the fewest images queued).
 The reference only has the offline batch script (``inference/run_inference.py``); this is its online
 counterpart for deployment. Requests are queued and a single GPU worker thread forms batches:
 
-* requests with the same sampling parameters (temperature, top-k, top-p) share a batch; the worker
+* requests with the same sampling parameters (temperature, top-k, top-p, guidance scale) share a batch; the worker
   waits at most ``--batch-window-ms`` for more work after the first request, up to ``--max-batch``
   images (the decode engine's skinny-GEMM path covers batches <= 64);
 * the batch is padded to the next power of two and run through a decode engine (two concurrent
   :class:`DecodeEngine` chains from batch 32 on) cached per
   padded size, so every shape's hipGraph is captured once and replayed for every later batch;
+* ``cond_scale`` other than 1 (classifier-free guidance) runs on a guided engine, cached per padded picture count
+  beside the plain ones; the scale itself is a device scalar, so every scale replays the same graph;
 * codes are decoded by the VQGAN and returned as base64 PNGs together with per-request timings.
 
 Endpoints: ``POST /generate`` ``{"prompts": [...], "images_per_prompt": 1, "temperature": 1.0,
-"top_k": 256, "top_p": 1.0}``, ``GET /health``, ``GET /stats``. ``create_app`` builds the app around
+"top_k": 256, "top_p": 1.0, "cond_scale": 1.0}``, ``GET /health``, ``GET /stats``. ``create_app`` builds the app around
 an already-loaded model (tests, embedding into another service); ``main`` loads weights like
 ``run_inference.py`` and starts uvicorn.
 """
@@ -53,7 +55,7 @@ def _png_b64(img: np.ndarray) -> str:
 
 
 class _Job:
-    def __init__(self, prompts: List[str], n: int, key: Tuple[float, int, float]):
+    def __init__(self, prompts: List[str], n: int, key: Tuple[float, int, float, float]):
         self.prompts, self.n, self.key = prompts, n, key
         self.future: Future = Future()
         self.t_submit = time.perf_counter()
@@ -72,6 +74,7 @@ class BatchingGenerator:
         self.window = batch_window_ms / 1000.0
         self.q: "queue.Queue[Optional[_Job]]" = queue.Queue()
         self.engines: Dict[int, DecodeEngine] = {}
+        self.guided_engines: Dict[int, DecodeEngine] = {}  # classifier-free guidance, by padded picture count
         self.stats = {"requests": 0, "images": 0, "batches": 0, "gpu_seconds": 0.0}
         self._held: List[_Job] = []  # popped while batching but with other sampling parameters
         self._thread = threading.Thread(target=self._loop, name="dalle-serve-worker", daemon=True)
@@ -79,8 +82,10 @@ class BatchingGenerator:
 
     # -- API ------------------------------------------------------------------------------------
     def submit(self, prompts: List[str], images_per_prompt: int = 1, temperature: float = 1.0, top_k: int = 0,
-               top_p: float = 1.0) -> Future:
-        job = _Job(list(prompts), int(images_per_prompt), (float(temperature), int(top_k), float(top_p)))
+               top_p: float = 1.0, cond_scale: float = 1.0) -> Future:
+        if cond_scale < 0:
+            raise ValueError("cond_scale must be >= 0")
+        job = _Job(list(prompts), int(images_per_prompt), (float(temperature), int(top_k), float(top_p), float(cond_scale)))
         if not job.prompts or job.n < 1:
             raise ValueError("need at least one prompt and images_per_prompt >= 1")
         if job.images > self.max_batch:
@@ -167,12 +172,15 @@ class BatchingGenerator:
             padded *= 2
         padded = min(padded, self.max_batch) if n <= self.max_batch else n
         ids = self._ids(prompts + [prompts[-1]] * (padded - n)).to(self.device)
-        eng = self.engines.get(padded)
+        temperature, top_k, top_p, cond_scale = batch[0].key
+        guided = cond_scale != 1.0
+        cache = self.guided_engines if guided else self.engines
+        eng = cache.get(padded)
         if eng is None:
-            eng = self.engines[padded] = make_decode_engine(self.model, padded, device=self.device)
-        temperature, top_k, top_p = batch[0].key
+            eng = cache[padded] = make_decode_engine(self.model, padded, device=self.device, **({"guided": True} if guided else {}))
+        kw = {"cond_scale": cond_scale} if guided else {}
         t0 = time.perf_counter()
-        codes = eng.generate(self.model.prepare_text(ids), temperature=temperature, top_k=top_k, top_p=top_p)[:n]
+        codes = eng.generate(self.model.prepare_text(ids), temperature=temperature, top_k=top_k, top_p=top_p, **kw)[:n]
         imgs = self.model.vae.decode(codes) if self.model.vae is not None else None
         if self.device.type == "cuda":
             torch.cuda.synchronize(self.device)
@@ -230,13 +238,13 @@ class MultiDeviceGenerator:
         return tot
 
     def submit(self, prompts: List[str], images_per_prompt: int = 1, temperature: float = 1.0, top_k: int = 0,
-               top_p: float = 1.0) -> Future:
+               top_p: float = 1.0, cond_scale: float = 1.0) -> Future:
         n = len(prompts) * int(images_per_prompt)
         with self._lock:
             i = min(range(len(self.gens)), key=lambda k: (self._inflight[k], k))
             self._inflight[i] += n
         try:
-            fut = self.gens[i].submit(prompts, images_per_prompt, temperature, top_k, top_p)
+            fut = self.gens[i].submit(prompts, images_per_prompt, temperature, top_k, top_p, cond_scale)
         except Exception:
             with self._lock:
                 self._inflight[i] -= n
@@ -273,6 +281,7 @@ try:  # the HTTP layer is optional: BatchingGenerator works without fastapi / py
         temperature: float = Field(1.0, ge=0.0)
         top_k: int = Field(0, ge=0)
         top_p: float = Field(1.0, gt=0.0, le=1.0)
+        cond_scale: float = Field(1.0, ge=0.0)
 except ImportError:  # pragma: no cover
     GenerateRequest = None
 
@@ -297,7 +306,7 @@ def create_app(gen):
     @app.post("/generate")
     def generate(req: GenerateRequest):
         try:
-            fut = gen.submit(req.prompts, req.images_per_prompt, req.temperature, req.top_k, req.top_p)
+            fut = gen.submit(req.prompts, req.images_per_prompt, req.temperature, req.top_k, req.top_p, req.cond_scale)
         except ValueError as e:
             raise HTTPException(status_code=400, detail=str(e))
         return fut.result()

@@ -44,12 +44,14 @@ class VQGanParams(nn.Module):
 
 
 class ModelWrapper(nn.Module):
-    def __init__(self, model):
+    def __init__(self, model, null_cond_prob: float = 0.0):
         super().__init__()
         self.model = model
+        self.null_cond_prob = float(null_cond_prob)  # caption dropout (classifier-free guidance), training only
 
     def forward(self, input_ids, attention_mask, image):
-        loss = self.model.forward(text=input_ids, image=image, mask=attention_mask, return_loss=True)
+        kw = {"null_cond_prob": self.null_cond_prob} if self.training and self.null_cond_prob > 0 else {}
+        loss = self.model.forward(text=input_ids, image=image, mask=attention_mask, return_loss=True, **kw)
         return {'loss': loss}
 
 
@@ -91,7 +93,7 @@ class TrainingTask:
         dalle.vae_params = vae
         n_trainable = sum(p.numel() for p in dalle.parameters() if p.requires_grad)
         logger.info(f"{n_trainable / 1e6:.1f}M trainable parameters ({n_trainable})")
-        self.model = ModelWrapper(dalle)
+        self.model = ModelWrapper(dalle, null_cond_prob=getattr(trainer_args, "null_cond_prob", 0.0))
 
         output_dir = Path(trainer_args.output_dir)
         # resume: the newest checkpoint* directory (by creation time) that holds a model_state.pt
