@@ -40,7 +40,7 @@ def main():
     X = torch.randn(M, 1024, device=dev).bfloat16()  # transpose input (the LN-output -> X^T pass)
     H = torch.randn(M // 2, 8192, device=dev).bfloat16()  # geglu_fwd input (half the micro-batch)
 
-    gemms = {"own_np": lambda: C.gemm_pt(A, B, None, 30, 0), "own_ps": lambda: C.gemm_pt(A, B, None, 20, 0),
+    gemms = {"own_np": lambda: C.gemm_pt(A, B, None, 10, 0), "own_ps": lambda: C.gemm_pt(A, B, None, 20, 0),
              "hipblaslt": lambda: torch.mm(A, B.t())}
     mems = {"transpose_x8": lambda: [C.transpose_act_bf16(X) for _ in range(8)],
             "geglu_fwd_x2": lambda: [C.geglu_fwd(H) for _ in range(2)]}

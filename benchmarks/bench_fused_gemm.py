@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Median time of the two fused-epilogue GEMMs at the bench24 B48 shapes (M = 61440 tokens):
-FF-out dgrad + GEGLU backward (ff_dgrad_geglu) and QKV + rotary into the attention layout (qkv_rope).
+FF-out dgrad + GEGLU backward (ff_dgrad_geglu) and QKV + rotary into the attention layout (qkv_rope_pt).
 One JSON line."""
 import json
 import os
@@ -9,8 +9,9 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from dalle_amd.models.rotary import rotary_tables  # noqa: E402
+from dalle_amd.models.patterns import AttnGeometry  # noqa: E402
 from dalle_amd.ops.ext import load_extension  # noqa: E402
+from dalle_amd.ops.hip_ops import rope_cs_table  # noqa: E402
 
 
 def timeit(fn, reps=20, warmup=3):
@@ -38,10 +39,10 @@ def main():
     h = torch.randn(M, 2 * F, device=dev).bfloat16()
     x = torch.randn(M, D, device=dev).bfloat16()
     wq = (torch.randn(3 * H * 64, D, device=dev) * 0.03).bfloat16()
-    cos, sin = rotary_tables(T, S, 64, device=dev)
+    cs = rope_cs_table(AttnGeometry(T, S), 64, dev)
     res = {}
     res["ff_dgrad_geglu_us"] = round(timeit(lambda: C.ff_dgrad_geglu(dy, w2t, h)), 1)
-    res["qkv_rope_us"] = round(timeit(lambda: C.qkv_rope(x, wq, cos, sin, T, S, H, n, False, 0.125)), 1)
+    res["qkv_rope_us"] = round(timeit(lambda: C.qkv_rope_pt(x, wq, cs, T, S, H, n, False, 0.125)), 1)
     print(json.dumps(res), flush=True)
 
 

@@ -36,12 +36,12 @@ size_t uq8_workspace_bytes();
 void uq8_dequant(const uint8_t*, const float*, float*, long, float, int, hipStream_t);
 void uq8_seg_compress(const float*, const long*, const long*, const int*, int, uint8_t*, float*, hipStream_t);
 void uq8_seg_dequant(const uint8_t*, const long*, const float*, const long*, const int*, int, float*, float, int, hipStream_t);
+bool gemm_qkv_rope(const void*, const void*, void*, void*, void*, const float*, const float*, int, int, int, int, int, int, int,
+                   float, hipStream_t);
 bool skinny_gemm(int, SkinnyArgs, hipStream_t);
 int skinny_ks(int, int, int, int);
 void skinny_force_config(int, int, int, int);
 std::vector<int> skinny_shape_info(int, int, int, int);
-bool gemm_qkv_rope(const void*, const void*, void*, void*, void*, const float*, const float*, int, int, int, int, int, int, int,
-                   float, hipStream_t);
 void splitk_accum(const float*, float*, long, int, int, hipStream_t);
 void psgd_orthonormalize(float*, const long*, const int*, int, int, float, hipStream_t);
 bool psgd_reconstruct(float*, float*, const float*, const float*, long, int, int, hipStream_t);
@@ -80,19 +80,13 @@ void decode_rope(const void*, const float*, const float*, void*, void*, void*, c
 void decode_attn(const void*, void*, void*, void*, const int*, const DecodeGeom&, int, hipStream_t, const int*, const int*);
 void vq_embed(const int64_t*, const float*, float*, int, int, int, hipStream_t);
 bool sample_step(const SampleArgs&, hipStream_t);
-bool gemm_geglu_bwd(const void*, const void*, const void*, void*, float*, int, int, int, hipStream_t, int);
+bool gemm_geglu_bwd(const void*, const void*, const void*, void*, float*, int, int, int, hipStream_t);
 void column_sum(const float*, int, int, const GradSink&, hipStream_t);
 bool gemm_pt(const void*, const void*, void*, const void*, int, int, int, int, int, int, hipStream_t);
 void gemm_set_cpol(int);
-void gemm_set_pt_overlap(int, int);
-void gemm_set_geglu_bwd_2wg(int);
-void gemm_set_2wg_stagger(int, int);
-bool gemm_2wg(const void*, const void*, void*, const void*, int, int, int, hipStream_t);
 void gemm_set_drain(int);
 bool gemm_pt_qkv_rope(const void*, const void*, void*, void*, void*, const float*, int, int, int, int, int, int, int, float,
                       hipStream_t, int);
-bool gemm_pt_geglu_bwd(const void*, const void*, const void*, void*, float*, int, int, int, hipStream_t, int);
-bool gemm_pt_geglu_fwd(const void*, const void*, const void*, void*, void*, int, int, int, hipStream_t, int);
 void permlane16_probe(unsigned*, hipStream_t);
 void rope_pad_zero(void*, void*, void*, int, int, int, int, hipStream_t);
 void lamb_grad_norm(const float*, long, float*, float, float*, float*, hipStream_t);
@@ -409,7 +403,7 @@ std::vector<Tensor> geglu_bwd_bias(Tensor h, Tensor dout, c10::optional<Tensor> 
 
 // FF-out dgrad GEMM with the GEGLU backward + FF-in bias grad in its epilogue (csrc/kernels/gemm.hip
 // EPI 2): dy (M, K) bf16, w2t = W2^T (F, K) bf16, h = FF-in pre-activation (M, 2F) -> (dh, dbias).
-std::vector<Tensor> ff_dgrad_geglu(Tensor dy, Tensor w2t, Tensor h, c10::optional<Tensor> gb, int64_t stagger) {
+std::vector<Tensor> ff_dgrad_geglu(Tensor dy, Tensor w2t, Tensor h, c10::optional<Tensor> gb) {
   CHECK_IN(dy, torch::kBFloat16); CHECK_IN(w2t, torch::kBFloat16); CHECK_IN(h, torch::kBFloat16);
   TORCH_CHECK(dy.dim() == 2 && w2t.dim() == 2 && h.dim() == 2, "ff_dgrad_geglu: 2-D operands");
   const long M = dy.size(0), K = dy.size(1), F = w2t.size(0);
@@ -424,7 +418,7 @@ std::vector<Tensor> ff_dgrad_geglu(Tensor dy, Tensor w2t, Tensor h, c10::optiona
     pb = db.data_ptr<float>();
   }
   TORCH_CHECK(dalle::gemm_geglu_bwd(dy.data_ptr(), w2t.data_ptr(), h.data_ptr(), dh.data_ptr(), part.data_ptr<float>(), M, F, K,
-                                    cur_stream(), (int)stagger), "ff_dgrad_geglu: unsupported shape");
+                                    cur_stream()), "ff_dgrad_geglu: unsupported shape");
   dalle::column_sum(part.data_ptr<float>(), M / 128, 2 * F, dalle::GradSink{pb, nullptr, nullptr, (int)(2 * F), db.defined() ? 0 : 1},
                     cur_stream());
   return {dh, db};
@@ -535,7 +529,9 @@ void splitk_accum_(Tensor acc, Tensor part, bool accumulate) {
   dalle::splitk_accum(part.data_ptr<float>(), acc.data_ptr<float>(), n, (int)part.size(0), accumulate ? 1 : 0, cur_stream());
 }
 
-// C = A . B^T (+ bias): A (M, K), B (N, K) bf16, both K-contiguous; M, N multiples of 256, K of 64
+// C = A . B^T (+ bias): A (M, K), B (N, K) bf16, both K-contiguous; M, N multiples of 256, K of 64.
+// variant 0 = the simple kernel, 200..207 = the 4-phase kernel, 300..332 / 401..432 = the 8-phase kernel in a tile
+// order (csrc/kernels/gemm.hip)
 Tensor gemm_nt(Tensor A, Tensor B, c10::optional<Tensor> bias, int64_t variant) {
   CHECK_IN(A, torch::kBFloat16); CHECK_IN(B, torch::kBFloat16);
   TORCH_CHECK(A.dim() == 2 && B.dim() == 2 && A.size(1) == B.size(1), "gemm_nt: A (M, K) and B (N, K)");
@@ -645,8 +641,9 @@ Tensor asm_gemm(Tensor A, Tensor B, c10::optional<Tensor> bias, c10::optional<Te
   return C;
 }
 
-// ---- persistent GEMM family (csrc/kernels/gemm_pt.hip): transposed accumulators, register-direct epilogues ----
-// C (M, N) = A (M, K) . B (N, K)^T (+ bias); variant 5 = main loop only (measurement)
+// ---- csrc/kernels/gemm_pt.hip: transposed accumulators, register-direct epilogues ----
+// C (M, N) = A (M, K) . B (N, K)^T (+ bias); variant 0 / 10 = one tile per workgroup, 20 = persistent;
+// group = tile order (0: the default)
 Tensor gemm_pt(Tensor A, Tensor B, c10::optional<Tensor> bias, int64_t variant, int64_t group) {
   CHECK_IN(A, torch::kBFloat16); CHECK_IN(B, torch::kBFloat16);
   TORCH_CHECK(A.dim() == 2 && B.dim() == 2 && A.size(1) == B.size(1), "gemm_pt: A (M, K) and B (N, K)");
@@ -654,23 +651,17 @@ Tensor gemm_pt(Tensor A, Tensor B, c10::optional<Tensor> bias, int64_t variant, 
   TORCH_CHECK(M % 256 == 0 && N % 256 == 0 && K % 64 == 0 && K >= 128, "gemm_pt: M, N multiples of 256, K of 64 (>= 128)");
   const void* bp = nullptr;
   if (bias.has_value() && bias->defined()) {
-    if (variant == 40 || variant == 41) {  // measurement: per-workgroup timestamps (int64, 5 per tile)
-      CHECK_IN((*bias), torch::kLong);
-      TORCH_CHECK(bias->numel() >= (int64_t)(M / 256) * (N / 256) * 5, "gemm_pt: stamps (tiles * 5,)");
-    } else {
-      CHECK_IN((*bias), torch::kBFloat16);
-      TORCH_CHECK(bias->numel() == N, "gemm_pt: bias (N,)");
-    }
+    CHECK_IN((*bias), torch::kBFloat16);
+    TORCH_CHECK(bias->numel() == N, "gemm_pt: bias (N,)");
     bp = bias->data_ptr();
   }
-  TORCH_CHECK(variant != 40 && variant != 41 || bp != nullptr, "gemm_pt: stamp variants need the stamp buffer");
   auto C = torch::empty({M, N}, A.options());
   TORCH_CHECK(dalle::gemm_pt(A.data_ptr(), B.data_ptr(), C.data_ptr(), bp, M, N, K, N, (int)variant, (int)group, cur_stream()),
-              "gemm_pt: unsupported shape");
+              "gemm_pt: unsupported shape or variant");
   return C;
 }
 
-// QKV projection + rotary (persistent kernel): cs = (n + 1, 32, 2) fp32 (cos, sin) per rotary pair
+// QKV projection + rotary (gemm_pt.hip): cs = (n + 1, 32, 2) fp32 (cos, sin) per rotary pair
 std::vector<Tensor> qkv_rope_pt(Tensor h, Tensor w, Tensor cs, int64_t T, int64_t S, int64_t H, int64_t n, bool col_major,
                                 double qscale, int64_t persist) {
   CHECK_IN(h, torch::kBFloat16); CHECK_IN(w, torch::kBFloat16); CHECK_IN(cs, torch::kFloat32);
@@ -689,49 +680,6 @@ std::vector<Tensor> qkv_rope_pt(Tensor h, Tensor w, Tensor cs, int64_t T, int64_
               "qkv_rope_pt: unsupported shape");
   dalle::rope_pad_zero(q.data_ptr(), k.data_ptr(), v.data_ptr(), g.Tp, T, g.Np, B * H, cur_stream());
   return {q, k, v};
-}
-
-// FF-out dgrad + GEGLU backward (persistent kernel): dy (M, K), w2t = W2^T (F, K), h (M, 2F) -> (dh, dbias)
-std::vector<Tensor> ff_dgrad_geglu_pt(Tensor dy, Tensor w2t, Tensor h, c10::optional<Tensor> gb, int64_t persist) {
-  CHECK_IN(dy, torch::kBFloat16); CHECK_IN(w2t, torch::kBFloat16); CHECK_IN(h, torch::kBFloat16);
-  TORCH_CHECK(dy.dim() == 2 && w2t.dim() == 2 && h.dim() == 2, "ff_dgrad_geglu_pt: 2-D operands");
-  const long M = dy.size(0), K = dy.size(1), F = w2t.size(0);
-  TORCH_CHECK(w2t.size(1) == K && h.size(0) == M && h.size(1) == 2 * F, "ff_dgrad_geglu_pt: shape mismatch");
-  TORCH_CHECK(M % 256 == 0 && F % 256 == 0 && K % 64 == 0 && K >= 128, "ff_dgrad_geglu_pt: M, F multiples of 256, K of 64");
-  auto dh = torch::empty_like(h);
-  auto part = torch::empty({M / 64, 2 * F}, h.options().dtype(torch::kFloat32));
-  float* pb = sink_ptr(gb, 2 * F, "ff_dgrad_geglu_pt dbias");
-  Tensor db;
-  if (!pb) {
-    db = torch::empty({2 * F}, h.options().dtype(torch::kFloat32));
-    pb = db.data_ptr<float>();
-  }
-  TORCH_CHECK(dalle::gemm_pt_geglu_bwd(dy.data_ptr(), w2t.data_ptr(), h.data_ptr(), dh.data_ptr(), part.data_ptr<float>(), M, F, K,
-                                       cur_stream(), (int)persist), "ff_dgrad_geglu_pt: unsupported shape");
-  dalle::column_sum(part.data_ptr<float>(), M / 64, 2 * F, dalle::GradSink{pb, nullptr, nullptr, (int)(2 * F), db.defined() ? 0 : 1},
-                    cur_stream());
-  return {dh, db};
-}
-
-// FF-in GEMM + GEGLU forward (persistent kernel): x (M, K), w1i / b1i = W1 / b1 rows interleaved per 64-row
-// group ([32 value | 32 gate]) -> a (M, 2F) pre-activation in the original [value | gate] order, u (M, F)
-std::vector<Tensor> ff_in_geglu_pt(Tensor x, Tensor w1i, c10::optional<Tensor> b1i, int64_t persist) {
-  CHECK_IN(x, torch::kBFloat16); CHECK_IN(w1i, torch::kBFloat16);
-  TORCH_CHECK(x.dim() == 2 && w1i.dim() == 2 && x.size(1) == w1i.size(1), "ff_in_geglu_pt: x (M, K), w1i (2F, K)");
-  const int M = x.size(0), K = x.size(1), F2 = w1i.size(0);
-  TORCH_CHECK(M % 256 == 0 && F2 % 256 == 0 && K % 64 == 0 && K >= 128, "ff_in_geglu_pt: M, 2F multiples of 256, K of 64");
-  const void* bp = nullptr;
-  if (b1i.has_value() && b1i->defined()) {
-    CHECK_IN((*b1i), torch::kBFloat16);
-    TORCH_CHECK(b1i->numel() == F2, "ff_in_geglu_pt: bias (2F,)");
-    bp = b1i->data_ptr();
-  }
-  auto a = torch::empty({M, F2}, x.options());
-  auto u = torch::empty({M, F2 / 2}, x.options());
-  TORCH_CHECK(dalle::gemm_pt_geglu_fwd(x.data_ptr(), w1i.data_ptr(), bp, a.data_ptr(), u.data_ptr(), M, F2 / 2, K, cur_stream(),
-                                       (int)persist),
-              "ff_in_geglu_pt: unsupported shape");
-  return {a, u};
 }
 
 Tensor permlane16_probe() {
@@ -1446,8 +1394,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("geglu_fwd", &geglu_fwd);
   m.def("geglu_bwd", &geglu_bwd);
   m.def("geglu_bwd_bias", &geglu_bwd_bias, py::arg("h"), py::arg("dout"), py::arg("gb") = py::none());
-  m.def("ff_dgrad_geglu", &ff_dgrad_geglu, py::arg("dy"), py::arg("w2t"), py::arg("h"), py::arg("gb") = py::none(),
-        py::arg("stagger") = -1);
+  m.def("ff_dgrad_geglu", &ff_dgrad_geglu, py::arg("dy"), py::arg("w2t"), py::arg("h"), py::arg("gb") = py::none());
   m.def("scale_residual_", &scale_residual_);
   m.def("scale_residual_out", &scale_residual_out);
   m.def("transpose_bf16", &transpose_bf16, "fp32 (R, C) -> bf16 (C, R) in one pass");
@@ -1467,22 +1414,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_nt", &gemm_nt, py::arg("A"), py::arg("B"), py::arg("bias") = py::none(), py::arg("variant") = 0);
   m.def("gemm_set_cpol", [](int64_t c) { dalle::gemm_set_cpol((int)c); }, py::arg("cpol"),
         "cache policy of the hand-written GEMMs' output stores: 0 plain, 1 sc0, 2 nt, 16 sc1, 17 sc0 sc1");
-  m.def("gemm_set_geglu_bwd_2wg", [](int64_t v) { dalle::gemm_set_geglu_bwd_2wg((int)v); }, py::arg("v"),
-        "1: FF-out dgrad + GEGLU backward on the two-workgroups-per-CU kernel");
-  m.def("gemm_set_2wg_stagger", [](int64_t ticks, int64_t first_wave) { dalle::gemm_set_2wg_stagger((int)ticks, (int)first_wave); },
-        py::arg("ticks"), py::arg("first_wave") = -256,
-        "two-workgroup GEMM start stagger: 10 ns ticks; first_wave < 0 delays workgroups [-fw, -2 fw), > 0 is 4-phase");
-  m.def("gemm_2wg", [](Tensor A, Tensor B) {
-    CHECK_IN(A, torch::kBFloat16); CHECK_IN(B, torch::kBFloat16);
-    TORCH_CHECK(A.dim() == 2 && B.dim() == 2 && A.size(1) == B.size(1), "gemm_2wg: A (M, K), B (N, K)");
-    auto C = torch::empty({A.size(0), B.size(0)}, A.options());
-    TORCH_CHECK(dalle::gemm_2wg(A.data_ptr(), B.data_ptr(), C.data_ptr(), nullptr, (int)A.size(0), (int)B.size(0), (int)A.size(1),
-                                cur_stream()), "gemm_2wg: M % 256, N % 128, K % 32 (K >= 64)");
-    return C;
-  });
-  m.def("gemm_set_pt_overlap", [](int64_t v, int64_t stagger) { dalle::gemm_set_pt_overlap((int)v, (int)stagger); },
-        py::arg("overlap"), py::arg("stagger_pct") = 0,
-        "persistent plain GEMM: epilogue stores beside the next tile's first K-step; start stagger in % of a tile");
   m.def("gemm_set_drain", [](int64_t d) { dalle::gemm_set_drain((int)d); }, py::arg("drain"),
         "1: hand-written GEMM workgroups wait for their output stores before ending");
   m.def("asm_gemm", &asm_gemm, py::arg("A"), py::arg("B"), py::arg("bias") = py::none(), py::arg("out") = py::none());
@@ -1494,9 +1425,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_pt", &gemm_pt, py::arg("A"), py::arg("B"), py::arg("bias") = py::none(), py::arg("variant") = 0, py::arg("group") = 0);
   m.def("qkv_rope_pt", &qkv_rope_pt, py::arg("h"), py::arg("w"), py::arg("cs"), py::arg("T"), py::arg("S"), py::arg("H"),
         py::arg("n"), py::arg("col_major"), py::arg("qscale"), py::arg("persist") = -1);
-  m.def("ff_dgrad_geglu_pt", &ff_dgrad_geglu_pt, py::arg("dy"), py::arg("w2t"), py::arg("h"), py::arg("gb") = py::none(),
-        py::arg("persist") = -1);
-  m.def("ff_in_geglu_pt", &ff_in_geglu_pt, py::arg("x"), py::arg("w1i"), py::arg("b1i") = py::none(), py::arg("persist") = -1);
   m.def("permlane16_probe", &permlane16_probe);
   m.def("xent_fwd_bwd_", &xent_fwd_bwd_);
   m.def("embed_fwd", &embed_fwd);

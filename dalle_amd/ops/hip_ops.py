@@ -202,7 +202,7 @@ def _rot_freqs(device) -> tuple:
 
 def rope_cs_table(geom: AttnGeometry, dim_head: int, device) -> torch.Tensor:
     """(n + 1, dim_head / 2, 2) fp32 (cos, sin) per rotary pair -- the packed form of the rotary tables
-    read by the persistent QKV GEMM's epilogue (pairs share their cos; the rotate_half sign is applied
+    read by the QKV GEMM's register epilogue (pairs share their cos; the rotate_half sign is applied
     in the kernel)."""
     key = (geom.text_len, geom.image_size, dim_head, str(device))
     t = _cs_tables.get(key)
@@ -254,10 +254,12 @@ def wgrad_splits(M: int, N: int, K: int) -> int:
     return s
 
 
-# the QKV projection runs on the hand-written GEMM with the rotary in its register epilogue, writing the attention
-# storage layout directly (csrc/kernels/gemm_pt.hip: 427 us vs 473 us for hipBLASLt + a rotary pass at the
-# bench24 B48 shape, profiles/r3_gemm_pt_vs_hipblaslt_8ph.jsonl); the rotary backward runs in the attention-
-# backward epilogues and the GEGLU backward in the FF-out dgrad GEMM's epilogue (csrc/kernels/gemm.hip EPI 2).
+# the QKV projection and the FF-out dgrad run on the assembly kernels (csrc/asm), with the rotary / the GEGLU
+# backward in their epilogues. Where those do not apply (d_model < 1024, DALLE_AMD_ASM_GEMM=0) the same fusions run
+# on the hand-written HIP GEMMs: QKV + rotary in the register epilogue of csrc/kernels/gemm_pt.hip, writing the
+# attention storage layout directly (427 us vs 473 us for hipBLASLt + a rotary pass at the bench24 B48 shape,
+# profiles/r3_gemm_pt_vs_hipblaslt_8ph.jsonl), and the GEGLU backward in the FF-out dgrad GEMM's epilogue
+# (csrc/kernels/gemm.hip EPI 2). The rotary backward runs in the attention-backward epilogues.
 
 
 # weight-grad inputs kept token-contiguous: the LN outputs feeding the QKV and FF-in GEMMs are saved as

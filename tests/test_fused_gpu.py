@@ -177,7 +177,8 @@ def test_ff_dgrad_geglu_epilogue(cuda, M, F, K):
     dy = (torch.randn(M, K, device=cuda) * 0.5).to(torch.bfloat16)
     w2 = torch.randn(K, F, device=cuda) * 0.03  # Linear(F -> K).weight
     h = torch.randn(M, 2 * F, device=cuda).to(torch.bfloat16)
-    dh, db = C.ff_dgrad_geglu(dy, w2.t().contiguous().to(torch.bfloat16), h)
+    w2t = w2.t().contiguous().to(torch.bfloat16)
+    dh, db = C.ff_dgrad_geglu(dy, w2t, h)
     du = torch.mm(dy, w2.to(torch.bfloat16))
     dh_ref, db_ref = C.geglu_bwd_bias(h, du)
     assert _rel(dh, dh_ref) < 1e-2 and _rel(db, db_ref) < 1e-2
@@ -187,3 +188,7 @@ def test_ff_dgrad_geglu_epilogue(cuda, M, F, K):
     out.backward(dy.float() @ w2.to(torch.bfloat16).float())
     assert _rel(dh, hf.grad) < 2e-2
     assert _rel(db, hf.grad.sum(0)) < 2e-2
+    # bias-grad accumulation into a sink (what the training step always passes)
+    sink = torch.ones(2 * F, device=cuda)
+    C.ff_dgrad_geglu(dy, w2t, h, sink)
+    assert _rel(sink - 1, db) < 1e-5

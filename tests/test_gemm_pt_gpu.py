@@ -1,7 +1,7 @@
 """Persistent GEMM family (csrc/kernels/gemm_pt.hip) against fp32 PyTorch references: the plain bf16
-product (+bias), QKV + 3-axis rotary into the attention storage, the FF-in GEMM + GEGLU forward and the
-FF-out dgrad + GEGLU backward. Shapes cover one tile per workgroup, several tiles per workgroup (the
-continuous cross-tile DMA stream), the XCD remap (tile count % 8 == 0) and its absence."""
+product (+bias) and QKV + 3-axis rotary into the attention storage. Shapes cover one tile per workgroup,
+several tiles per workgroup (the persistent form's continuous cross-tile DMA stream), the XCD remap
+(tile count % 8 == 0) and its absence."""
 import pytest
 import torch
 
@@ -60,15 +60,13 @@ def test_gemm_pt(cuda, M, N, K, group, variant):
     assert torch.equal(got, C().gemm_pt(A, B, None, variant, group))
 
 
-@pytest.mark.parametrize("attn_type", ["axial_row", "axial_col", "conv_like"])
-@pytest.mark.parametrize("persist", [0, 1])
-def test_qkv_rope_pt(cuda, attn_type, persist):
+def _check_qkv_rope_pt(cuda, attn_type, persist, T, B):
     from dalle_amd.ops.hip_ops import C, _rope_tables, rope_cs_table
 
     torch.manual_seed(0)
-    T, S, H, D = 65, 16, 4, 256
+    S, H, D = 16, 4, 256
     geom = AttnGeometry(T, S, 5)
-    n, B = T + S * S - 1, 8  # M = 2560: several tiles per workgroup on small grids
+    n = T + S * S - 1
     h = torch.randn(B * n, D, device=cuda).bfloat16()
     w = (0.05 * torch.randn(3 * H * 64, D, device=cuda)).bfloat16()
     cos, sin = _rope_tables(geom, 64, cuda)
@@ -86,34 +84,18 @@ def test_qkv_rope_pt(cuda, attn_type, persist):
         assert ((got.float() - ref.float()).abs() <= 0.02 * ref.float().abs().max()).all()
 
 
-@pytest.mark.parametrize("M,F,K", [(512, 1024, 256), (2560, 4096, 1024)])
+@pytest.mark.parametrize("attn_type", ["axial_row", "axial_col", "conv_like"])
 @pytest.mark.parametrize("persist", [0, 1])
-def test_ff_dgrad_geglu_pt(cuda, M, F, K, persist):
-    from dalle_amd.ops import hip_ops
+def test_qkv_rope_pt(cuda, attn_type, persist):
+    _check_qkv_rope_pt(cuda, attn_type, persist, 65, 8)  # n = 320, M = 2560: several tiles per workgroup on small grids
 
-    torch.manual_seed(5)
-    C = hip_ops.C()
-    dy = (torch.randn(M, K, device=cuda) * 0.5).to(torch.bfloat16)
-    w2 = torch.randn(K, F, device=cuda) * 0.03
-    h = torch.randn(M, 2 * F, device=cuda).to(torch.bfloat16)
-    w2t = w2.t().contiguous().to(torch.bfloat16)
-    dh, db = C.ff_dgrad_geglu_pt(dy, w2t, h, None, persist)
-    dh_old, db_old = C.ff_dgrad_geglu(dy, w2t, h)
-    assert _rel(dh, dh_old) < 1e-2 and _rel(db, db_old) < 1e-2
-    if persist == 0:
-        # one tile per workgroup: the 8-phase kernel's LDS-staged epilogue on the same bf16 du -- equal up to
-        # the compiler's contraction of the GELU multiply-adds (one bf16 ulp); bias sums in another order
-        assert ((dh.float() - dh_old.float()).abs() <= 2 ** -7 * dh_old.float().abs() + 1e-6).all()
-        assert _rel(db, db_old) < 1e-5
-    hf = h.float().requires_grad_(True)
-    out = hf[:, :F] * torch.nn.functional.gelu(hf[:, F:])
-    out.backward(dy.float() @ w2.to(torch.bfloat16).float())
-    assert _rel(dh, hf.grad) < 2e-2
-    assert _rel(db, hf.grad.sum(0)) < 2e-2
-    # bias-grad accumulation into a sink
-    sink = torch.ones(2 * F, device=cuda)
-    C.ff_dgrad_geglu_pt(dy, w2t, h, sink, persist)
-    assert _rel(sink - 1, db) < 1e-5
+
+@pytest.mark.parametrize("attn_type", ["axial_row", "axial_col", "conv_like"])
+def test_qkv_rope_pt_n322(cuda, attn_type):
+    """n = 322 (n % 16 == 2, M = 41216 = 161 * 256): rows 8 apart in a 16-row sub-tile can belong to two samples, so
+    the epilogue takes its 16-row x 64-byte stores instead of whole lines -- what production runs whenever
+    n % 16 != 0."""
+    _check_qkv_rope_pt(cuda, attn_type, 0, 67, 128)
 
 
 @pytest.mark.parametrize("cpol", [0, 1, 2, 16, 17])
@@ -123,6 +105,7 @@ def test_store_policy_and_drain_bitwise(cuda, cpol, drain):
     end-of-workgroup store drain (gemm_set_drain) change how the epilogue writes, never what: every
     hand-written GEMM form is bitwise equal to the plain-store, no-drain result."""
     from dalle_amd.ops import hip_ops
+    from dalle_amd.ops.hip_ops import rope_cs_table
 
     C = hip_ops.C()
     torch.manual_seed(1)
@@ -133,13 +116,17 @@ def test_store_policy_and_drain_bitwise(cuda, cpol, drain):
     dy = (0.5 * torch.randn(M, K, device=cuda)).bfloat16()
     w2t = (0.05 * torch.randn(N, K, device=cuda)).bfloat16()
     a = torch.randn(M, 2 * N, device=cuda).bfloat16()
+    # the QKV + rotary geometry of test_qkv_rope_pt
+    T, S, H, D, nb = 65, 16, 4, 256, 8
+    n = T + S * S - 1
+    hq = torch.randn(nb * n, D, device=cuda).bfloat16()
+    wq = (0.05 * torch.randn(3 * H * 64, D, device=cuda)).bfloat16()
+    cs = rope_cs_table(AttnGeometry(T, S, 5), 64, cuda)
 
     def run_all():
         outs = [C.gemm_pt(A, B, bias, 10, 0), C.gemm_pt(A, B, bias, 20, 0), C.gemm_nt(A, B, None, 300)]
-        dh8 = C.ff_dgrad_geglu(dy, w2t, a, None, 0)
-        dhp = C.ff_dgrad_geglu_pt(dy, w2t, a)
-        outs += list(dh8) if isinstance(dh8, (tuple, list)) else [dh8]
-        outs += list(dhp) if isinstance(dhp, (tuple, list)) else [dhp]
+        outs += list(C.ff_dgrad_geglu(dy, w2t, a, None))
+        outs += list(C.qkv_rope_pt(hq, wq, cs, T, S, H, n, False, 0.125, 0))
         return [o.clone() for o in outs]
 
     try:
@@ -154,27 +141,3 @@ def test_store_policy_and_drain_bitwise(cuda, cpol, drain):
         C.gemm_set_drain(1)
     for r, g in zip(ref, got):
         assert torch.equal(r, g)
-
-
-@pytest.mark.parametrize("M,F,K", [(512, 1024, 256), (2560, 4096, 1024)])
-def test_ff_dgrad_geglu_two_workgroup_bitwise(cuda, M, F, K):
-    """The two-workgroups-per-CU FF-out dgrad + GEGLU backward (gemm_set_geglu_bwd_2wg) walks K in the same
-    32-deep chunks as the 8-phase kernel and shares its epilogue: bitwise equal dh and bias partials. The
-    plain two-workgroup product against an fp32 reference."""
-    from dalle_amd.ops import hip_ops
-
-    C = hip_ops.C()
-    torch.manual_seed(13)
-    dy = (torch.randn(M, K, device=cuda) * 0.5).bfloat16()
-    w2t = (torch.randn(F, K, device=cuda) * 0.03).bfloat16()
-    h = torch.randn(M, 2 * F, device=cuda).bfloat16()
-    try:
-        C.gemm_set_geglu_bwd_2wg(0)
-        dh0, db0 = C.ff_dgrad_geglu(dy, w2t, h)
-        C.gemm_set_geglu_bwd_2wg(1)
-        dh1, db1 = C.ff_dgrad_geglu(dy, w2t, h)
-    finally:
-        C.gemm_set_geglu_bwd_2wg(0)
-    assert torch.equal(dh0, dh1) and torch.equal(db0, db1)
-    got = C.gemm_2wg(dy, w2t)
-    assert _rel(got, dy.float() @ w2t.float().t()) < 5e-3
