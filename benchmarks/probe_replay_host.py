@@ -82,7 +82,7 @@ def main():
     env = {k: v for k, v in os.environ.items() if k.startswith(("DEBUG_", "PROBE_", "DALLE_AMD_"))}
     print(json.dumps({"probe": "decode graph replay, host submit vs GPU", "batch": B, "model": cfg.depth, "env": env,
                       "parts": getattr(eng, "nparts", 1),
-                      "graphs": getattr(eng, "graph_mode", "linear"), "results": res}), flush=True)
+                      "graphs": "per-part" if hasattr(eng, "parts") else "linear", "results": res}), flush=True)
 
 
 if __name__ == "__main__":

@@ -66,7 +66,7 @@ struct SkinnyArgs {
   int steps;         // 128-wide K chunks per wave (set by skinny_gemm)
   float* ws;         // KS * (N / 16) * ceil16(M) * 16 * (1 or 2) floats
   int* cnt;          // >= N / 16 zero-initialised counters (self-resetting)
-  void* out;         // EPI 0 (bf16 or fp32), EPI 1 (bf16)
+  void* out;         // EPI 0 (bf16 or fp32), EPI 1 (bf16), EPI 4 (fp32 slabs (KS, M, N))
   int out_f32;
   float* resid;        // EPI 2: resid += scale * (y + bias), fp32 (M, N)
   const float* scale;
@@ -78,17 +78,6 @@ struct SkinnyArgs {
   const int* pos;
   int H, n;
   float qscale;
-  int dbg;  // benchmark-only: bit 0 skips the X loads, bit 1 the W loads
-  // EPI 5 (split-K slabs + LayerNorm tail): the slabs (a.out) are stored write-through, every workgroup
-  // takes a ticket on *cnt, and the last M arrivers each finish one row: resid += scale * (sum + bias),
-  // then the decode LayerNorm + cached token shift of that row (ln_w / ln_b, LN history `hist` (M, n, N)
-  // bf16 at *pos, shifted row to `y` (M, N) bf16); T / S: text length / image side, shift: 0 = plain LN
-  const float* ln_w;
-  const float* ln_b;
-  void* hist;
-  void* y;
-  int T, S, shift;
-  unsigned* err;  // set to 1 if a tail's wait for the other workgroups gave up (bounded spin)
 };
 
 // Fused decode sampler (sample.hip): top-k / top-p / temperature / Gumbel-max + token bookkeeping.

@@ -47,22 +47,30 @@ def gumbel_sample(logits: torch.Tensor, temperature: float = 1.0, generator=None
     return torch.argmax(logits / max(temperature, 1e-10) - torch.log(-torch.log(u)), dim=-1)
 
 
+def _guidance_scale(guided: bool, cond_scale: Optional[float]) -> Optional[float]:
+    """The ``cond_scale`` argument of a ``generate`` call, checked: the scale a guided engine's captured step
+    reads (default 1), None for a plain engine (which takes no scale)."""
+    if not guided:
+        if cond_scale is not None:
+            raise ValueError("cond_scale needs an engine built with guided=True")
+        return None
+    s = 1.0 if cond_scale is None else float(cond_scale)
+    if s < 0:
+        raise ValueError(f"cond_scale must be >= 0, got {s}")
+    return s
+
+
 class DecodeEngine:
     def __init__(self, model, batch_size: int, device=None, use_hip: Optional[bool] = None, skinny: bool = True,
-                 partials: int = 2, fused_sampler: bool = True, ln_tail: Optional[bool] = None, guided: bool = False):
+                 partials: int = 2, fused_sampler: bool = True, guided: bool = False):
         """``guided``: classifier-free guidance. The engine then owns ``2 * batch_size`` rows -- the pictures' captions
         on top, the null caption below -- and samples picture ``r`` from ``u + cond_scale * (c - u)`` of rows ``r`` /
         ``r + batch_size`` (in the fused sampler's one launch), feeding the chosen code back to both rows.
         ``skinny``: decode projections on the skinny MFMA GEMM with fused epilogues (when the shapes allow);
         ``partials``: 2 = every projection leaves split-K slabs summed by its consumer (measured fastest,
-        profiles/r2_decode_partials_ab.txt), 1 = the residual projections only, 0 = in-GEMM split-K hand-off;
-        ``fused_sampler``: the one-kernel top-k / top-p / Gumbel sampler (K18); ``ln_tail`` (None: env
-        DALLE_AMD_DECODE_LN_TAIL, default off): the out-proj / FF-out slabs and the next LayerNorm + shift in ONE
-        launch (skinny EPI 5: the projection's last workgroups finish the rows) instead of the projection
-        plus a decode_ln_shift launch -- 5 instead of 7 launches per layer, but measured slower
-        (profiles/r6_decode_ln_tail.txt: 14.2 vs 16.8 images/s at batch 64; the in-launch hand-off's
-        write-through, ticket, poll and read-back round trips cost more than the kernel boundary they remove).
-        The non-default forms are kept for the numerics A/B in tests/test_generation_gpu.py."""
+        profiles/r2_decode_partials_ab.txt), 1 = the residual projections only, 0 = in-GEMM split-K hand-off
+        (the non-default forms are kept for the numerics A/B in tests/test_generation_gpu.py);
+        ``fused_sampler``: the one-kernel top-k / top-p / Gumbel sampler (K18)."""
         self.model = model
         cfg = self.cfg = model.cfg
         self.B = batch_size  # pictures, as callers see it; R rows of caches, histories and buffers
@@ -129,21 +137,8 @@ class DecodeEngine:
         mode = int(partials) if self.skinny else 0
         self.partials = mode in (1, 2)
         self.qkv_partials = mode == 2
-        # pending residual update of a stream, not yet applied: ("part", stream, slabs, bias, LayerScale) -- slabs
-        # already computed -- or ("gemm", stream, X, W, bias, LayerScale) -- the projection itself deferred, so
-        # that it runs as one launch with the LayerNorm that reads the stream (skinny_partials_ln_)
+        # pending residual update of a stream, not yet applied: (stream, slabs, bias, LayerScale) or None
         self._pending = None
-        if ln_tail is None:
-            ln_tail = os.environ.get("DALLE_AMD_DECODE_LN_TAIL", "0") == "1"
-        self.ln_tail = False
-        if self.partials and ln_tail:
-            from ..ops.hip_ops import C
-            ok = C().skinny_partials_ln_ok
-            self.ln_tail = ok(B, self.d, self.H * self.Dh) and ok(B, self.d, cfg.ff_mult * self.d)
-        # one ticket word per fused launch site of a step (2 per layer), zeroed per generate call; error word
-        self.ln_cnt = torch.zeros(2 * L + 2, dtype=torch.int32, device=dev) if self.ln_tail else None
-        self.ln_err = torch.zeros(1, dtype=torch.int32, device=dev) if self.ln_tail else None
-        self._site = 0
 
     # -- weights (one bf16 cast per generate call) --------------------------------------------------
     def _wt(self, p):
@@ -165,41 +160,22 @@ class DecodeEngine:
                 w.copy_(p.detach().reshape(w.shape))
         for k in self.kc + self.vc:
             k.zero_()
-        if self.ln_cnt is not None:
-            self.ln_cnt.zero_()
-            self.ln_err.zero_()
 
     # -- branch steps -------------------------------------------------------------------------------
     def _flush_pending(self):
         if self._pending is not None:
             from ..ops.hip_ops import C
-            kind, x, *rest = self._pending
+            C().residual_from_partials_(*self._pending)
             self._pending = None
-            if kind == "gemm":
-                X, W, bias, scale = rest
-                C().residual_from_partials_(x, C().skinny_partials(X, W), bias, scale)
-            else:
-                part, bias, scale = rest
-                C().residual_from_partials_(x, part, bias, scale)
 
     def _ln_shift(self, ls, hist, x):
         pre = ls.fn
         if self.use_hip:
             from ..ops.hip_ops import C
-            pend = self._pending
-            if pend is not None and pend[1] is not x:
+            if self._pending is not None and self._pending[0] is not x:  # another stream's update: apply it now
                 self._flush_pending()
-                pend = None
+            part, pbias, pscale = self._pending[1:] if self._pending is not None else (None, None, None)
             self._pending = None
-            if pend is not None and pend[0] == "gemm":
-                _, _, X, W, pbias, pscale = pend
-                site = self._site
-                self._site += 1
-                C().skinny_partials_ln_(X, W, pbias, pscale, x, pre.norm.weight.detach(), pre.norm.bias.detach(), hist,
-                                        self.hbuf, self.pos, self.T, self.S, bool(pre.fn.enabled),
-                                        self.ln_cnt[site:site + 1], self.ln_err)
-                return self.hbuf
-            part, pbias, pscale = (pend[2], pend[3], pend[4]) if pend is not None else (None, None, None)
             C().decode_ln_shift_(x, pre.norm.weight.detach(), pre.norm.bias.detach(), hist, self.hbuf, self.pos,
                                  self.T, self.S, bool(pre.fn.enabled), part, pbias, pscale)
             return self.hbuf
@@ -235,13 +211,9 @@ class DecodeEngine:
                                  self.pos, self.H, self.Dh ** -0.5, self.sk_cnt)
             C().decode_attn_(self.qbuf, self.kc[li], self.vc[li], self.obuf, self.pos, self.T, self.S, self.H,
                              self.geom.kernel_size, PATTERN_IDS[attn.attn_type], **self._text_kw())
-        if self.ln_tail:
-            self._pending = ("gemm", x_res, self.obuf, self._wt(attn.to_out[0].weight), self._wt(attn.to_out[0].bias),
-                             self._scale(ls))
-            return x_res
         if self.partials:
             po = C().skinny_partials(self.obuf, self._wt(attn.to_out[0].weight))
-            self._pending = ("part", x_res, po, self._wt(attn.to_out[0].bias), self._scale(ls))
+            self._pending = (x_res, po, self._wt(attn.to_out[0].bias), self._scale(ls))
             return x_res
         C().skinny_residual_(x_res, self.obuf, self._wt(attn.to_out[0].weight), self._wt(attn.to_out[0].bias),
                              self._scale(ls), self.sk_cnt)
@@ -255,11 +227,8 @@ class DecodeEngine:
         ff = ls.fn.fn.fn
         h = self._ln_shift(ls, self.hist[li][1], x_in)
         a = C().skinny_geglu(h, self._wt(ff.net[0].weight), self._wt(ff.net[0].bias), self.sk_cnt)
-        if self.ln_tail:
-            self._pending = ("gemm", x_res, a, self._wt(ff.net[3].weight), self._wt(ff.net[3].bias), self._scale(ls))
-            return x_res
         if self.partials:
-            self._pending = ("part", x_res, C().skinny_partials(a, self._wt(ff.net[3].weight)), self._wt(ff.net[3].bias),
+            self._pending = (x_res, C().skinny_partials(a, self._wt(ff.net[3].weight)), self._wt(ff.net[3].bias),
                              self._scale(ls))
             return x_res
         C().skinny_residual_(x_res, a, self._wt(ff.net[3].weight), self._wt(ff.net[3].bias), self._scale(ls), self.sk_cnt)
@@ -334,7 +303,6 @@ class DecodeEngine:
         W = self.model.to_logits[1].weight
         x = F.embedding(self.tok, W.detach()).float()
         self._pending = None
-        self._site = 0
         if self.cfg.reversible:
             x1, x2 = x, x.clone()
             for li, (f, g) in enumerate(self.pairs):
@@ -626,12 +594,8 @@ class DecodeEngine:
         function of (seed, position, row, token), so positions >= k draw what an unprimed call draws there.
         ``cond_scale`` (guided engines only): the guidance scale, a device scalar the captured step reads -- another
         scale replays the same graph; 1 samples from the conditional rows' logits, 0 from the null caption's."""
-        if cond_scale is not None and not self.guided:
-            raise ValueError("cond_scale needs an engine built with guided=True")
-        if self.guided:
-            s = 1.0 if cond_scale is None else float(cond_scale)
-            if s < 0:
-                raise ValueError(f"cond_scale must be >= 0, got {s}")
+        s = _guidance_scale(self.guided, cond_scale)
+        if s is not None:
             self.cond_scale.fill_(s)
         self.temperature, self.top_k, self.top_p = temperature, top_k, top_p
         if seed is None:
@@ -692,7 +656,7 @@ class DecodeEngine:
 
 class _PartGraphs:
     """One image-position step of every part: each part's own captured graph replayed on the part's stream
-    (the ``graph`` of a :class:`SplitDecodeEngine` in per-part mode)."""
+    (the ``graph`` of a :class:`SplitDecodeEngine`)."""
 
     def __init__(self, eng):
         self.eng = eng
@@ -709,15 +673,12 @@ class SplitDecodeEngine:
     parts share the bf16 weight copies; each has its own KV caches, LN histories, device position and
     sampler seed (``seed + part``), so the parts never touch the same buffer.
 
-    ``graphs`` (``DALLE_AMD_DECODE_GRAPHS``): "per-part" (default) captures each part's step as its own
-    LINEAR graph, replayed on the part's stream with no per-step join -- the HIP runtime launches a linear
-    graph from pre-built packets, 0.17 ms of host time per step for both parts. "joint": one graph with the
-    parts as parallel branches joined at the end of every step -- the runtime launches a multi-branch graph
-    node by node, ~2.5 ms of host time per ~3 ms step, so the host barely stays ahead and its jitter reaches
-    the GPU (profiles/r6_decode_replay_host.txt: 3.00-3.02 vs 3.05-3.11 ms per step)."""
+    Each part's step is captured as its own LINEAR graph, replayed on the part's stream with no per-step join:
+    the HIP runtime launches a linear graph from pre-built packets, 0.17 ms of host time per step for both
+    parts. (One graph with the parts as parallel branches is launched node by node, ~2.5 ms of host time per
+    ~3 ms step: profiles/r6_decode_replay_host.txt, 3.00-3.02 vs 3.05-3.11 ms per step.)"""
 
-    def __init__(self, model, batch_size: int, device=None, parts: int = 2, graphs: Optional[str] = None,
-                 guided: bool = False):
+    def __init__(self, model, batch_size: int, device=None, parts: int = 2, guided: bool = False):
         """``guided``: every part is a guided engine over its slice of the pictures, with its own conditional and
         null rows, so no part reads another's buffers."""
         if batch_size % parts:
@@ -730,11 +691,6 @@ class SplitDecodeEngine:
             p._refresh_weights = False
         self.device = self.parts[0].device
         self.use_hip = self.parts[0].use_hip
-        if graphs is None:
-            graphs = os.environ.get("DALLE_AMD_DECODE_GRAPHS", "per-part")
-        if graphs not in ("per-part", "joint"):
-            raise ValueError(f"DALLE_AMD_DECODE_GRAPHS={graphs!r}: expected per-part or joint")
-        self.graph_mode = graphs
         self.graph = None
         self._graph_cfg = None
         self._part_streams = None
@@ -792,36 +748,11 @@ class SplitDecodeEngine:
         cfg = (self.parts[0].temperature, self.parts[0].top_k, self.parts[0].top_p)
         if self.graph is not None and self._graph_cfg == cfg:
             return
-        if self.graph_mode == "per-part":
-            for p in self.parts:
-                p._capture()  # a linear graph of the part's own step (its warm-up steps are reset by the prefill)
-            if self._part_streams is None:
-                self._part_streams = [torch.cuda.Stream() for _ in self.parts]
-            self.graph = _PartGraphs(self)
-            self._graph_cfg = cfg
-            return
-        main = torch.cuda.current_stream()
-        streams = [torch.cuda.Stream() for _ in self.parts[1:]]
-        warm = torch.cuda.Stream()
-        warm.wait_stream(main)
-        with torch.cuda.stream(warm):
-            for _ in range(2):
-                for p in self.parts:
-                    p._step()
-        main.wait_stream(warm)
-        g = torch.cuda.CUDAGraph()
-        with _CAPTURE_LOCK, torch.cuda.graph(g, capture_error_mode="thread_local"):
-            cap = torch.cuda.current_stream()
-            for s in streams:
-                s.wait_stream(cap)
-            self.parts[0]._step()
-            for p, s in zip(self.parts[1:], streams):
-                with torch.cuda.stream(s):
-                    p._step()
-            for s in streams:
-                cap.wait_stream(s)
-        self.graph = g
-        self._streams = streams
+        for p in self.parts:
+            p._capture()  # a linear graph of the part's own step (its warm-up steps are reset by the prefill)
+        if self._part_streams is None:
+            self._part_streams = [torch.cuda.Stream() for _ in self.parts]
+        self.graph = _PartGraphs(self)
         self._graph_cfg = cfg
 
     @torch.no_grad()
@@ -830,12 +761,8 @@ class SplitDecodeEngine:
                  prime: Optional[torch.Tensor] = None, cond_scale: Optional[float] = None) -> torch.Tensor:
         if prime is not None and (prime.dim() != 2 or prime.shape[0] != self.B):
             raise ValueError(f"prime must be (batch {self.B}, k), got {tuple(prime.shape)}")
-        if cond_scale is not None and not self.guided:
-            raise ValueError("cond_scale needs an engine built with guided=True")
-        if self.guided:
-            s = 1.0 if cond_scale is None else float(cond_scale)
-            if s < 0:
-                raise ValueError(f"cond_scale must be >= 0, got {s}")
+        s = _guidance_scale(self.guided, cond_scale)
+        if s is not None:
             for p in self.parts:
                 p.cond_scale.fill_(s)
         if seed is None:
@@ -862,13 +789,9 @@ class SplitDecodeEngine:
         return self.codes.clone()
 
     def replay_steps(self, k: int):
-        """``k`` decode steps through the captured graph(s). Per-part: the part streams fork from the current
-        stream, each replays its part's graph ``k`` times with no join in between, and the current stream
-        joins them at the end (the codes are read there)."""
-        if self.graph_mode == "joint":
-            for _ in range(k):
-                self.graph.replay()
-            return
+        """``k`` decode steps through the captured graphs: the part streams fork from the current stream, each
+        replays its part's graph ``k`` times with no join in between, and the current stream joins them at the
+        end (the codes are read there)."""
         main = torch.cuda.current_stream()
         for st in self._part_streams:
             st.wait_stream(main)

@@ -112,6 +112,140 @@ def test_skinny_qkv_rope(cuda, M, H):
     assert kc.abs().sum() == 0
 
 
+@pytest.mark.parametrize("M,N,K,slabs", [(3, 48, 256, 1), (17, 512, 384, 3), (33, 256, 1024, 4), (64, 1024, 4096, 8)])
+def test_skinny_partials(cuda, M, N, K, slabs):
+    """The split-K slabs the decode step's QKV / out-proj / FF-out projections leave (skinny EPI 4): all three
+    M-block counts, 1 / 2 / 4 waves per workgroup, a row count that is no multiple of 16. bf16 x bf16 products are
+    exact in fp32, so only the K additions round: elementwise |sum_k part[k] - ref| <= 2 K 2^-24 (|x| @ |w|^T)
+    against float64 (the 2 covers a truncating accumulator as well as round-to-nearest)."""
+    from dalle_amd.ops.hip_ops import C
+
+    torch.manual_seed(0)
+    x = torch.randn(M, K, device=cuda).bfloat16()
+    w = (0.05 * torch.randn(N, K, device=cuda)).bfloat16()
+    part = C().skinny_partials(x, w)
+    assert part.shape == (slabs, M, N) and part.dtype == torch.float32  # (M, N) per slab: no padded rows exist
+    ref = x.double() @ w.double().t()
+    bound = 2 * K * 2.0 ** -24 * (x.double().abs() @ w.double().abs().t())
+    err = (part.double().sum(0) - ref).abs()
+    print(f"skinny_partials {(M, N, K)}: {slabs} slabs, largest error / bound = {(err / bound).max().item():.3e}")
+    assert (err <= bound).all()
+    for _ in range(3):
+        assert torch.equal(C().skinny_partials(x, w), part)
+
+
+LN_T, LN_S = 17, 8
+LN_N = LN_T + LN_S * LN_S - 1
+
+
+def _ln_shift_ref(xn, w, b, hist, pos, shift):
+    """DecodeEngine._ln_shift's CPU branch in float64: the LN row (the history row at ``pos``) and the shifted row."""
+    D = xn.shape[-1]
+    y = torch.nn.functional.layer_norm(xn, (D,), w, b, 1e-5)
+    out = y.clone()
+    if shift:
+        q, h2 = D // 4, D // 2
+        if pos < LN_T:
+            out[:, :h2] = hist[:, pos - 1, :h2] if pos >= 1 else 0.0
+        else:
+            k = pos - LN_T
+            out[:, :q] = hist[:, pos - LN_S, :q] if k >= LN_S else 0.0
+            out[:, q:h2] = hist[:, pos - 1, q:h2] if k % LN_S else 0.0
+    return y, out
+
+
+@pytest.mark.parametrize("KS", [1, 3, 16])
+@pytest.mark.parametrize("D", [256, 1024])
+def test_slab_consumers(cuda, D, KS):
+    """The kernels that apply a pending residual update x += scale * (sum of slabs + bias): residual_from_partials_
+    and decode_ln_shift_ with pending slabs (one wave per row and four; 16 slabs is the binding's cap), with and
+    without bias, at a text position with no shift source (0) and with one (5), the first image token (both
+    sources absent), the first column of the second image row (upper source only) and a position with both.
+    x within the fp32 rounding of KS - 1 slab additions, the bias, the scale and the residual addition (KS + 3
+    covers them) against float64; LN history row and output within the project's bf16 LayerNorm bound (0.05 at
+    test_prefill_kernels_match_torch's input scales: half a bf16 ulp below 16 is 0.031)."""
+    from dalle_amd.ops.hip_ops import C
+
+    g = torch.Generator().manual_seed(0)
+    B, n = 3, LN_N
+    x0 = (torch.randn(B, D, generator=g) * 2 + 0.5).to(cuda)
+    w, b = torch.randn(D, generator=g).to(cuda), torch.randn(D, generator=g).to(cuda)
+    scale = torch.rand(D, generator=g).to(cuda)
+    bias = torch.randn(D, generator=g).bfloat16().to(cuda)
+    part = torch.randn(KS, B, D, generator=g).to(cuda)
+    hist0 = torch.randn(B, n, D, generator=g).bfloat16().to(cuda)
+    for pb in (bias, None):
+        pb64 = pb.double() if pb is not None else torch.zeros(D, dtype=torch.float64, device=cuda)
+        xn = x0.double() + scale.double() * (part.double().sum(0) + pb64)
+        xbound = (KS + 3) * 2.0 ** -24 * (x0.double().abs() + scale.double().abs() * (part.double().abs().sum(0) + pb64.abs()))
+        x = x0.clone()
+        C().residual_from_partials_(x, part, pb, scale)
+        assert ((x.double() - xn).abs() <= xbound).all()
+        for pos in (0, 5, LN_T, LN_T + LN_S, LN_T + LN_S + 3):
+            for shift in (True, False):
+                x, hist = x0.clone(), hist0.clone()
+                y = torch.zeros(B, D, dtype=torch.bfloat16, device=cuda)
+                p = torch.tensor(pos, dtype=torch.int32, device=cuda)
+                C().decode_ln_shift_(x, w, b, hist, y, p, LN_T, LN_S, shift, part, pb, scale)
+                ry, rout = _ln_shift_ref(xn, w.double(), b.double(), hist0.double(), pos, shift)
+                assert ry.abs().max().item() < 16  # the inputs: where 0.05 is above the bf16 rounding
+                assert ((x.double() - xn).abs() <= xbound).all()
+                assert (hist[:, pos].double() - ry).abs().max().item() < 0.05
+                assert (y.double() - rout).abs().max().item() < 0.05
+                hist[:, pos] = hist0[:, pos]
+                assert torch.equal(hist, hist0)  # no other history row touched
+        # past the cache end: the kernel returns before its first load
+        x, hist = x0.clone(), hist0.clone()
+        y = torch.zeros(B, D, dtype=torch.bfloat16, device=cuda)
+        C().decode_ln_shift_(x, w, b, hist, y, torch.tensor(n, dtype=torch.int32, device=cuda), LN_T, LN_S, True, part, pb, scale)
+        assert torch.equal(x, x0) and torch.equal(hist, hist0) and y.abs().sum().item() == 0
+
+
+def _attn_part_case(cuda, KS, T, S, Ks, pattern, positions):
+    """decode_attn_part_ (q / k / v summed from the QKV slabs in the attention's prologue) against the path it
+    replaces: decode_rope_ on the slab sum rounded to bf16, then decode_attn_."""
+    from dalle_amd.models.patterns import PATTERN_IDS
+    from dalle_amd.models.rotary import rotary_tables
+    from dalle_amd.ops.hip_ops import C
+
+    torch.manual_seed(0)
+    B, H = 3, 4
+    n = T + S * S - 1
+    cos, sin = rotary_tables(T, S, 64, device=cuda)
+    part = torch.randn(KS, B, 3 * H * 64, device=cuda)
+    kc0 = torch.randn(B * H, n, 64, device=cuda).bfloat16()
+    vc0 = torch.randn(B * H, n, 64, device=cuda).bfloat16()
+    qkv = part.sum(0).bfloat16()
+    for pos in positions:
+        pos = n - 1 if pos is None else pos
+        p = torch.tensor(pos, dtype=torch.int32, device=cuda)
+        kc, vc = kc0.clone(), vc0.clone()
+        out = torch.zeros(B, H * 64, dtype=torch.bfloat16, device=cuda)
+        C().decode_attn_part_(part, cos, sin, 0.125, kc, vc, out, p, T, S, H, Ks, PATTERN_IDS[pattern])
+        q2 = torch.zeros(B * H, 64, dtype=torch.bfloat16, device=cuda)
+        kc2, vc2, out2 = kc0.clone(), vc0.clone(), torch.zeros_like(out)
+        C().decode_rope_(qkv, cos, sin, q2, kc2, vc2, p, H, 0.125)
+        C().decode_attn_(q2, kc2, vc2, out2, p, T, S, H, Ks, PATTERN_IDS[pattern])
+        assert _rel(out, out2) < 1e-2, (pattern, pos)
+        assert _rel(kc[:, pos], kc2[:, pos]) < 1e-2 and _rel(vc[:, pos], vc2[:, pos]) < 1e-2
+        kc[:, pos], vc[:, pos] = kc0[:, pos], vc0[:, pos]
+        assert torch.equal(kc, kc0) and torch.equal(vc, vc0)  # no other cache row touched
+
+
+@pytest.mark.parametrize("pattern", ["full", "axial_row", "axial_col", "conv_like"])
+@pytest.mark.parametrize("KS", [1, 3])
+def test_decode_attn_part(cuda, KS, pattern):
+    """A text position, image positions in the first and second row, and the last position of the sequence."""
+    T, S = 17, 8
+    _attn_part_case(cuda, KS, T, S, 5, pattern, (5, T + 3, T + 11, None))
+
+
+@pytest.mark.parametrize("KS", [1, 3])
+def test_decode_attn_part_long_full(cuda, KS):
+    """Full attention over 301 and 1101 keys: up to and past one 320-key chunk (the chunked two-pass path)."""
+    _attn_part_case(cuda, KS, 257, 32, 11, "full", (300, 1100))
+
+
 @pytest.mark.parametrize("pattern,pos", [("full", 1100), ("full", 300), ("axial_row", 1000), ("axial_col", 900),
                                          ("conv_like", 700), ("axial_row", 100)])
 def test_decode_attention_kernel(cuda, pattern, pos):
