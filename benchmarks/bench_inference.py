@@ -37,6 +37,17 @@ def main():
     ap.add_argument("--no-share-src", action="store_true",
                     help="guided: every row reads the text keys from its own cache (default: null rows from the first "
                          "null row, caption rows from row 0 when the captions are equal)")
+    ap.add_argument("--inpaint-rows", default=None, metavar="A:B",
+                    help="inpainting: regenerate grid rows A..B-1 of a fixed random picture, keep the rest "
+                         "(DALLE.generate_images(img=..., img_mask=...))")
+    ap.add_argument("--no-prefill-kept", action="store_true",
+                    help="inpainting: the kept codes before the region go through decode steps, not the batched prefill")
+    ap.add_argument("--no-skip-tail", action="store_true",
+                    help="inpainting: run the decode steps after the region's last position too")
+    ap.add_argument("--inpaint-ab", type=int, default=0, metavar="N",
+                    help="N rounds over the generation modes, alternating (sampling only, no VAE decode): full; 448 forced "
+                         "codes as decode steps; the same as a suffix mask through the batched prefill; --inpaint-rows "
+                         "(default 8:24) with both savings, with skip_tail only, with neither. Prints medians and spread")
     ap.add_argument("--profile-steps", type=int, default=0,
                     help="batched caption prefill + N image-position decode steps (graph replays unless --no-graph), "
                          "then exit (rocprof)")
@@ -53,6 +64,21 @@ def main():
     from dalle_amd.models.generation import make_decode_engine
     guided = args.cond_scale != 1.0
     gen_kw = {"cond_scale": args.cond_scale} if guided else {}
+    S, L = cfg.image_fmap_size, cfg.image_seq_len
+    picture = torch.randint(0, cfg.num_image_tokens, (args.batch, L), device=dev,
+                            generator=torch.Generator(device=dev).manual_seed(1))
+
+    def rows_mask(spec):
+        a, b = (int(v) for v in spec.split(":"))
+        if not 0 <= a < b <= S:
+            raise SystemExit(f"--inpaint-rows {spec}: need 0 <= A < B <= {S}")
+        m = torch.zeros(args.batch, S, S, dtype=torch.bool, device=dev)
+        m[:, a:b] = True
+        return m
+
+    if args.inpaint_rows:
+        gen_kw.update(img=picture, img_mask=rows_mask(args.inpaint_rows), prefill_kept=not args.no_prefill_kept,
+                      skip_tail=not args.no_skip_tail)
     eng = make_decode_engine(model, args.batch, device=dev, **({"guided": True} if guided else {}))
     if guided:
         model._guided_decode_engine = eng
@@ -73,6 +99,38 @@ def main():
     torch.cuda.synchronize()
     print(f"# batched prefill of {cfg.text_len} caption positions: {(time.perf_counter() - t) * 1e3:.1f} ms", file=sys.stderr,
           flush=True)
+    if args.inpaint_ab:
+        k = int(0.4375 * L)
+        band = rows_mask(args.inpaint_rows or f"{S // 4}:{3 * S // 4}")
+        base = {"cond_scale": args.cond_scale} if guided else {}
+        variants = [
+            ("full generation", {}),
+            (f"prefix {k} as decode steps", dict(img=picture, num_init_img_tokens=k)),
+            (f"suffix mask from {k}, prefill_kept", dict(img=picture, img_mask=torch.arange(L, device=dev).expand(args.batch, L) >= k)),
+            ("rows band, prefill_kept + skip_tail", dict(img=picture, img_mask=band)),
+            ("rows band, skip_tail only", dict(img=picture, img_mask=band, prefill_kept=False)),
+            ("rows band, neither", dict(img=picture, img_mask=band, prefill_kept=False, skip_tail=False)),
+        ]
+        times = {name: [] for name, _ in variants}
+        for rnd in range(args.inpaint_ab + 1):  # round 0 is the warm-up of every variant
+            for name, kw in variants:
+                torch.cuda.synchronize()
+                t = time.perf_counter()
+                model.generate_images(text, top_k=args.top_k, use_graph=use_graph, return_codes=True, **base, **kw)
+                torch.cuda.synchronize()
+                if rnd:
+                    times[name].append(time.perf_counter() - t)
+            print(f"# round {rnd} done", file=sys.stderr, flush=True)
+        res = {}
+        for name, ts in times.items():
+            ts = sorted(ts)
+            res[name] = {"median_s": round(ts[len(ts) // 2], 4), "min_s": round(ts[0], 4), "max_s": round(ts[-1], 4),
+                         "calls": len(ts)}
+            print(f"# {name:40s} median {res[name]['median_s']:.4f} s  [{ts[0]:.4f}, {ts[-1]:.4f}]  n={len(ts)}", file=sys.stderr)
+        print(json.dumps({"metric": "generation modes, seconds per call (sampling only, alternating rounds)", "batch": args.batch,
+                          "model": args.model, "top_k": args.top_k, "rows": args.inpaint_rows or f"{S // 4}:{3 * S // 4}",
+                          "decode_parts": parts, "graph": use_graph, "variants": res}), flush=True)
+        return
     if args.profile_steps:
         # image positions only (the text-key part of every sparse pattern is read from here on)
         if use_graph and hasattr(eng, "replay_steps"):

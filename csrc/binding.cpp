@@ -66,8 +66,9 @@ void decode_ln_shift(float*, const float*, const float*, void*, void*, const int
                      const float*, const void*, const float*, int);
 void residual_from_partials(float*, const float*, const void*, const float*, int, int, int, hipStream_t);
 void prefill_rope(const void*, const float*, const float*, void*, void*, void*, int, int, int, int, float, hipStream_t);
-void prefill_ln_shift(const float*, const float*, const float*, void*, void*, int, int, int, int, float, int, hipStream_t);
+void prefill_ln_shift(const float*, const float*, const float*, void*, void*, int, int, int, int, float, int, int, int, hipStream_t);
 void prefill_softmax(const float*, const bool*, void*, long, int, hipStream_t);
+void prefill_softmax_block(const float*, const bool*, void*, long, int, int, int, int, hipStream_t);
 void prefill_residual(float*, const void*, const float*, long, int, hipStream_t);
 void decode_attn_part(const float*, int, const float*, const float*, float, void*, void*, void*, const int*, const DecodeGeom&, int,
                       hipStream_t, const int*, const int*);
@@ -1141,8 +1142,9 @@ void prefill_rope_(Tensor qkv, Tensor cosT, Tensor sinT, Tensor q, Tensor kc, Te
                       B, P, H, kc.size(1), (float)qscale, cur_stream());
 }
 
-// caption prefill: LN + text shift of x (B, P, D) fp32 -> hist[:, :P] (B, n, D) bf16 (unshifted) and out (B, P, D) bf16
-void prefill_ln_shift_(Tensor x, Tensor w, Tensor b, Tensor hist, Tensor out, bool shift, double eps) {
+// caption prefill: LN + text shift of x (B, P, D) fp32 -> hist[:, :P] (B, n, D) bf16 (unshifted) and out (B, P, D) bf16.
+// T >= 0: rows p >= T are image positions of an S-wide grid and take the image shift (T < 0: every row is text)
+void prefill_ln_shift_(Tensor x, Tensor w, Tensor b, Tensor hist, Tensor out, bool shift, double eps, int64_t T, int64_t S) {
   CHECK_IN(x, torch::kFloat32); CHECK_IN(w, torch::kFloat32); CHECK_IN(b, torch::kFloat32);
   CHECK_IN(hist, torch::kBFloat16); CHECK_IN(out, torch::kBFloat16);
   TORCH_CHECK(x.dim() == 3, "prefill_ln_shift: x (B, P, D)");
@@ -1150,8 +1152,10 @@ void prefill_ln_shift_(Tensor x, Tensor w, Tensor b, Tensor hist, Tensor out, bo
   TORCH_CHECK(D == 256 || D == 512 || D == 1024 || D == 2048, "prefill_ln_shift: unsupported hidden size");
   TORCH_CHECK(w.numel() == D && b.numel() == D && out.sizes() == x.sizes() && hist.dim() == 3 && hist.size(0) == B &&
               hist.size(1) >= P && hist.size(2) == D, "prefill_ln_shift: shapes");
+  if (T < 0 || T >= P) { T = P; S = 1; }  // no image rows
+  TORCH_CHECK(T >= 1 && S >= 1, "prefill_ln_shift: image rows need T >= 1 text positions and a grid width S >= 1");
   dalle::prefill_ln_shift(x.data_ptr<float>(), w.data_ptr<float>(), b.data_ptr<float>(), hist.data_ptr(), out.data_ptr(), B, P,
-                          hist.size(1), D, (float)eps, shift ? 1 : 0, cur_stream());
+                          hist.size(1), D, (float)eps, shift ? 1 : 0, (int)T, (int)S, cur_stream());
 }
 
 // caption prefill: masked row softmax of fp32 scores (R, P, P) -> bf16, mask (>= P, >= P) bool, row i of a (P, P) block
@@ -1164,6 +1168,20 @@ void prefill_softmax_(Tensor sc, Tensor mask, Tensor out) {
   TORCH_CHECK(P <= 512, "prefill_softmax: at most 512 keys");
   TORCH_CHECK(mask.dim() == 2 && mask.size(0) == P && mask.size(1) == P && mask.is_contiguous(), "prefill_softmax: mask (P, P) contiguous");
   dalle::prefill_softmax(sc.data_ptr<float>(), mask.data_ptr<bool>(), out.data_ptr(), (long)sc.size(0) * P, P, cur_stream());
+}
+
+// prefill over kept image codes: masked row softmax of the fp32 scores (R, Q, Pk) of queries q0 .. q0 + Q - 1 against keys
+// 0 .. Pk - 1 -> bf16; query q0 + i reads row q0 + i of the layer's static mask (M, M'), M >= q0 + Q, M' >= Pk
+void prefill_softmax_block_(Tensor sc, Tensor mask, Tensor out, int64_t q0) {
+  CHECK_IN(sc, torch::kFloat32); CHECK_IN(out, torch::kBFloat16); CHECK_CUDA(mask);
+  TORCH_CHECK(mask.scalar_type() == torch::kBool, "prefill_softmax_block: mask must be bool");
+  TORCH_CHECK(sc.dim() == 3 && out.sizes() == sc.sizes() && sc.numel() > 0, "prefill_softmax_block: sc / out (R, Q, Pk)");
+  const int Q = sc.size(1), Pk = sc.size(2);
+  TORCH_CHECK(Pk <= 2048, "prefill_softmax_block: at most 2048 keys");
+  TORCH_CHECK(mask.dim() == 2 && mask.is_contiguous() && q0 >= 0 && q0 + Q <= mask.size(0) && Pk <= mask.size(1),
+              "prefill_softmax_block: mask (>= q0 + Q, >= Pk) contiguous");
+  dalle::prefill_softmax_block(sc.data_ptr<float>(), mask.data_ptr<bool>(), out.data_ptr(), (long)sc.size(0) * Q, Q, Pk, (int)q0,
+                               (int)mask.size(1), cur_stream());
 }
 
 // caption prefill: x += scale * y (x fp32, y bf16, same shape (.., D); scale (D,) fp32)
@@ -1201,7 +1219,8 @@ void decode_attn_(Tensor q, Tensor kc, Tensor vc, Tensor out, Tensor pos, int64_
 // bookkeeping at device position *pos (codes[:, pos - T + 1] = sample, tok = next input token).
 Tensor sample_step(Tensor logits, int64_t top_k, double top_p, double temperature, Tensor seed, Tensor pos,
                    c10::optional<Tensor> text, c10::optional<Tensor> codes, c10::optional<Tensor> tok, int64_t vt,
-                   c10::optional<Tensor> prime, c10::optional<Tensor> n_prime, c10::optional<Tensor> cond_scale) {
+                   c10::optional<Tensor> prime, c10::optional<Tensor> n_prime, c10::optional<Tensor> cond_scale,
+                   c10::optional<Tensor> keep) {
   CHECK_IN(logits, torch::kFloat32); CHECK_IN(seed, torch::kInt64); CHECK_IN(pos, torch::kInt32);
   TORCH_CHECK(logits.dim() == 2 && logits.size(1) >= 1 && logits.size(1) <= 8192, "sample: logits must be (B, V <= 8192)");
   TORCH_CHECK(seed.numel() == 1 && pos.numel() == 1, "sample: seed / pos are device scalars");
@@ -1245,6 +1264,17 @@ Tensor sample_step(Tensor logits, int64_t top_k, double top_p, double temperatur
                 "sample: prime (B, image_len), n_prime a device scalar");
     a.prime = prime->data_ptr<int64_t>();
     a.n_prime = n_prime->data_ptr<int>();
+  }
+  if (keep.has_value()) {  // per-picture positions that take prime's code as well (inpainting)
+    TORCH_CHECK(prime.has_value(), "sample: keep needs prime and n_prime (the table the kept codes come from)");
+    const bool u8 = keep->scalar_type() == torch::kUInt8 || keep->scalar_type() == torch::kBool;
+    TORCH_CHECK(u8, "sample: keep must be uint8 or bool");
+    TORCH_CHECK(keep->is_cuda() && keep->device() == logits.device(), "sample: keep must be on the logits' device");
+    TORCH_CHECK(keep->is_contiguous(), "sample: keep must be contiguous");
+    const int pictures = a.cond_scale != nullptr ? a.b : B;
+    TORCH_CHECK(keep->dim() == 2 && keep->size(0) == pictures && keep->size(1) == a.img_len,
+                "sample: keep must be (pictures, image_len)");
+    a.keep = static_cast<const uint8_t*>(keep->data_ptr());
   }
   auto out = torch::empty({a.cond_scale != nullptr ? a.b : B}, logits.options().dtype(torch::kInt64));  // guided: (b,)
   a.sampled = out.data_ptr<int64_t>();
@@ -1403,8 +1433,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("pbias") = py::none(), py::arg("pscale") = py::none());
   m.def("decode_rope_", &decode_rope_);
   m.def("prefill_rope_", &prefill_rope_);
-  m.def("prefill_ln_shift_", &prefill_ln_shift_);
+  m.def("prefill_ln_shift_", &prefill_ln_shift_, py::arg("x"), py::arg("w"), py::arg("b"), py::arg("hist"), py::arg("out"),
+        py::arg("shift"), py::arg("eps"), py::arg("T") = -1, py::arg("S") = 1);
   m.def("prefill_softmax_", &prefill_softmax_);
+  m.def("prefill_softmax_block_", &prefill_softmax_block_, py::arg("sc"), py::arg("mask"), py::arg("out"), py::arg("q0"));
   m.def("prefill_residual_", &prefill_residual_);
   m.def("decode_attn_", &decode_attn_, py::arg("q"), py::arg("kc"), py::arg("vc"), py::arg("out"), py::arg("pos"), py::arg("T"),
         py::arg("S"), py::arg("H"), py::arg("K"), py::arg("pattern"), py::arg("text_shared") = py::none(),
@@ -1424,7 +1456,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("sample_step", &sample_step, py::arg("logits"), py::arg("top_k"), py::arg("top_p"), py::arg("temperature"),
         py::arg("seed"), py::arg("pos"), py::arg("text") = py::none(), py::arg("codes") = py::none(),
         py::arg("tok") = py::none(), py::arg("vt") = 0, py::arg("prime") = py::none(), py::arg("n_prime") = py::none(),
-        py::arg("cond_scale") = py::none());
+        py::arg("cond_scale") = py::none(), py::arg("keep") = py::none());
   m.def("lamb_grad_norm", &lamb_grad_norm);
   m.def("lamb_step", &lamb_step);
 }

@@ -196,10 +196,16 @@ void prefill_rope(const void* qkv, const float* cosT, const float* sinT, void* q
 // hist is (B, n, D)) and out (B, P, D) bf16 with the shift applied by push: channels [0, D/2) of row p land
 // in row p + 1 and row 0 gets zeros there (shift = 0: out = the LN output). Replaces the PyTorch chain
 // layer_norm -> bf16 cast -> history copy -> clone -> two slice copies (six passes over the rows).
+// Rows p >= T are image positions k = p - T of an S-wide grid (a prefill that runs on over kept image codes) and
+// follow decode_ln_shift_kernel's source rule, still by push: row p sends channels [0, D/4) to row p + S (the cell
+// above) when it is an image row, channels [D/4, D/2) to row p + 1 unless that row starts a grid row, and a text
+// row pushes only while p + 1 < T. A row whose rule names no source (grid row 0, grid column 0, position 0) writes
+// its own zeros, so every (row, channel range) of out has exactly one writer. T >= P: the caption-only form.
 template <int D>
 __global__ __launch_bounds__(256) void prefill_ln_shift_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                                const float* __restrict__ bias, __bf16* __restrict__ hist,
-                                                               __bf16* __restrict__ out, int B, int P, int n, float eps, int shift) {
+                                                               __bf16* __restrict__ out, int B, int P, int n, float eps, int shift,
+                                                               int T, int S) {
   constexpr int PER = D / 256;  // float4 per lane
   const int row = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63;
   if (row >= B * P) return;
@@ -232,8 +238,17 @@ __global__ __launch_bounds__(256) void prefill_ln_shift_kernel(const float* __re
     const s16x4 pk = pack4(o);
     *reinterpret_cast<s16x4*>(hr + c) = pk;
     if (shift && c < D / 2) {
-      if (p + 1 < P) *reinterpret_cast<s16x4*>(orow + D + c) = pk;
-      if (p == 0) *reinterpret_cast<s16x4*>(orow + c) = s16x4{};
+      if (p < T) {  // text row: the next text row takes these channels; position 0 has no source
+        if (p + 1 < T && p + 1 < P) *reinterpret_cast<s16x4*>(orow + D + c) = pk;
+        if (p == 0) *reinterpret_cast<s16x4*>(orow + c) = s16x4{};
+      } else if (c < D / 4) {  // image row: the cell below takes these; grid row 0 has none above
+        if (p + S < P) *reinterpret_cast<s16x4*>(orow + (size_t)S * D + c) = pk;
+        if (p - T < S) *reinterpret_cast<s16x4*>(orow + c) = s16x4{};
+      } else {  // image row: the cell to the right takes these; grid column 0 has none to its left
+        const int k = p - T;
+        if (p + 1 < P && (k + 1) % S != 0) *reinterpret_cast<s16x4*>(orow + D + c) = pk;
+        if (k % S == 0) *reinterpret_cast<s16x4*>(orow + c) = s16x4{};
+      }
     } else {
       *reinterpret_cast<s16x4*>(orow + c) = pk;
     }
@@ -241,13 +256,13 @@ __global__ __launch_bounds__(256) void prefill_ln_shift_kernel(const float* __re
 }
 
 void prefill_ln_shift(const float* x, const float* w, const float* b, void* hist, void* out, int B, int P, int n, int D, float eps,
-                      int shift, hipStream_t st) {
+                      int shift, int T, int S, hipStream_t st) {
   const dim3 grid(((long)B * P + 3) / 4);
   switch (D) {
-    case 256: hipLaunchKernelGGL(prefill_ln_shift_kernel<256>, grid, dim3(256), 0, st, x, w, b, (__bf16*)hist, (__bf16*)out, B, P, n, eps, shift); break;
-    case 512: hipLaunchKernelGGL(prefill_ln_shift_kernel<512>, grid, dim3(256), 0, st, x, w, b, (__bf16*)hist, (__bf16*)out, B, P, n, eps, shift); break;
-    case 1024: hipLaunchKernelGGL(prefill_ln_shift_kernel<1024>, grid, dim3(256), 0, st, x, w, b, (__bf16*)hist, (__bf16*)out, B, P, n, eps, shift); break;
-    case 2048: hipLaunchKernelGGL(prefill_ln_shift_kernel<2048>, grid, dim3(256), 0, st, x, w, b, (__bf16*)hist, (__bf16*)out, B, P, n, eps, shift); break;
+    case 256: hipLaunchKernelGGL(prefill_ln_shift_kernel<256>, grid, dim3(256), 0, st, x, w, b, (__bf16*)hist, (__bf16*)out, B, P, n, eps, shift, T, S); break;
+    case 512: hipLaunchKernelGGL(prefill_ln_shift_kernel<512>, grid, dim3(256), 0, st, x, w, b, (__bf16*)hist, (__bf16*)out, B, P, n, eps, shift, T, S); break;
+    case 1024: hipLaunchKernelGGL(prefill_ln_shift_kernel<1024>, grid, dim3(256), 0, st, x, w, b, (__bf16*)hist, (__bf16*)out, B, P, n, eps, shift, T, S); break;
+    case 2048: hipLaunchKernelGGL(prefill_ln_shift_kernel<2048>, grid, dim3(256), 0, st, x, w, b, (__bf16*)hist, (__bf16*)out, B, P, n, eps, shift, T, S); break;
   }
 }
 
@@ -289,6 +304,55 @@ __global__ __launch_bounds__(256) void prefill_softmax_kernel(const float* __res
 
 void prefill_softmax(const float* sc, const bool* mask, void* out, long rows, int P, hipStream_t st) {
   hipLaunchKernelGGL(prefill_softmax_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, sc, mask, (__bf16*)out, rows, P);
+}
+
+// ---- the same for a block of queries against up to 2048 keys (a prefill that runs on over kept image codes):
+// scores (R, Q, Pk) of queries q0 .. q0 + Q - 1 against keys 0 .. Pk - 1; query q0 + i reads row q0 + i of the
+// layer's static mask (row stride ldm >= Pk). One wave per row, 64 * NT >= Pk columns in registers. ----
+template <int NT>
+__global__ __launch_bounds__(256) void prefill_softmax_block_kernel(const float* __restrict__ sc, const bool* __restrict__ mask,
+                                                                    __bf16* __restrict__ out, long rows, int Q, int Pk, int q0,
+                                                                    int ldm) {
+  const long row = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int lane = threadIdx.x & 63;
+  if (row >= rows) return;
+  const int i = q0 + (int)(row % Q);
+  const float* sr = sc + row * Pk;
+  const bool* mr = mask + (size_t)i * ldm;
+  float v[NT];
+  float m = -INFINITY;
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    const int j = lane + 64 * t;
+    v[t] = (j < Pk && mr[min(j, Pk - 1)]) ? sr[min(j, Pk - 1)] : -INFINITY;
+    m = fmaxf(m, v[t]);
+  }
+  m = wave_max(m);
+  float s = 0.f;
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    v[t] = v[t] == -INFINITY ? 0.f : __expf(v[t] - m);
+    s += v[t];
+  }
+  s = wave_sum(s);
+  const float inv = s > 0.f ? 1.0f / s : 0.f;
+  __bf16* orow = out + row * Pk;
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    const int j = lane + 64 * t;
+    if (j < Pk) orow[j] = (__bf16)(v[t] * inv);
+  }
+}
+
+void prefill_softmax_block(const float* sc, const bool* mask, void* out, long rows, int Q, int Pk, int q0, int ldm,
+                           hipStream_t st) {
+  const dim3 grid((rows + 3) / 4);
+  if (Pk <= 512)
+    hipLaunchKernelGGL(prefill_softmax_block_kernel<8>, grid, dim3(256), 0, st, sc, mask, (__bf16*)out, rows, Q, Pk, q0, ldm);
+  else if (Pk <= 1024)
+    hipLaunchKernelGGL(prefill_softmax_block_kernel<16>, grid, dim3(256), 0, st, sc, mask, (__bf16*)out, rows, Q, Pk, q0, ldm);
+  else
+    hipLaunchKernelGGL(prefill_softmax_block_kernel<32>, grid, dim3(256), 0, st, sc, mask, (__bf16*)out, rows, Q, Pk, q0, ldm);
 }
 
 // ---- batched caption prefill: the residual update x += scale * y of a sublayer (y: the projection's bf16

@@ -97,6 +97,7 @@ struct SampleArgs {
   int64_t* sampled;     // (B,) the raw sample, may be null
   const int64_t* prime; // (B, img_len) forced image codes, may be null
   const int* n_prime;   // device scalar: image positions [0, *n_prime) take prime's code instead of the sample
+  const uint8_t* keep;  // (pictures, img_len), may be null: nonzero = this position takes prime's code too
   // classifier-free guidance (may be null: off). With it B = 2 b rows: [0, b) conditional, [b, 2 b) unconditional;
   // workgroup r samples from u + *cond_scale * (c - u) of rows r / r + b and writes both rows' codes and tokens
   const float* cond_scale;  // device scalar

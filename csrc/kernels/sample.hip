@@ -16,7 +16,9 @@
 // Finally thread 0 writes the image code of this position and the next input token (the next caption
 // token during prefill, else the sample shifted into the image vocabulary). With a `prime` table the first
 // *n_prime image positions take the table's code in place of the sample (image-primed generation; the count is
-// a device scalar, so one captured graph serves every prefix length).
+// a device scalar, so one captured graph serves every prefix length). A `keep` table (pictures, img_len) next to it
+// marks further positions, per picture, that take the table's code (inpainting: everything outside the region that is
+// redrawn); it is read from device memory each step, so the same graph serves masked and unmasked calls.
 // Guided (classifier-free guidance, `cond_scale` given): the logits are (2 b, V), conditional rows on top of the
 // unconditional ones; workgroup r of b forms m = u + s * (c - u) from rows r and r + b in three separately rounded
 // fp32 operations while loading, samples from m exactly as above (noise keyed by r) and writes the code and the next
@@ -250,9 +252,11 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(SampleArgs a) {
     for (int w = 1; w < SMP_NW; ++w)
       if (redf[w] > best || (redf[w] == best && redi[w] < besti)) { best = redf[w]; besti = redi[w]; }
     int64_t nxt = besti;
-    if (a.prime != nullptr) {  // forced prefix: image position ci < *n_prime takes the given code, not the sample
+    if (a.prime != nullptr) {  // forced: image position ci < *n_prime, or one the keep table marks, takes the given code
       const int ci = pos - (a.T - 1);
-      if (ci >= 0 && ci < min(*a.n_prime, a.img_len)) nxt = a.prime[(size_t)row * a.img_len + ci];
+      if (ci >= 0 && ci < a.img_len &&
+          (ci < *a.n_prime || (a.keep != nullptr && a.keep[(size_t)row * a.img_len + ci] != 0)))
+        nxt = a.prime[(size_t)row * a.img_len + ci];
     }
     if (a.sampled) a.sampled[row] = nxt;
     if (a.codes) {

@@ -226,6 +226,25 @@ class SharedEmbedding(nn.Module):
         return F.embedding(ids, self.weight)
 
 
+def code_mask(img_mask: torch.Tensor, batch: int, fmap_size: int, image_size: Optional[int] = None) -> torch.Tensor:
+    """An inpainting mask as (batch, fmap_size ** 2) bool over the image codes, True = regenerate. Accepted layouts,
+    told apart by size: (b, n) or (b, g, g) over the codes (g = ``fmap_size``), (b, S, S) or (b, 1, S, S) over the
+    pixels (S = ``image_size``, the VAE's); a code cell is regenerated if any of its pixels is marked (max-pool)."""
+    g, S = int(fmap_size), image_size
+    m = torch.as_tensor(img_mask)
+    if m.dim() < 2 or m.shape[0] != batch:
+        raise ValueError(f"img_mask must have the batch size {batch} first, got {tuple(m.shape)}")
+    m = m != 0
+    shape = tuple(m.shape[1:])
+    if shape == (g * g,) or shape == (g, g):
+        return m.reshape(batch, g * g)
+    if S is not None and S != g and S % g == 0 and shape in ((S, S), (1, S, S)):
+        f = S // g
+        return m.reshape(batch, g, f, g, f).any(4).any(2).reshape(batch, g * g)
+    sizes = f"(b, {g * g}), (b, {g}, {g})" + ("" if S is None else f", (b, {S}, {S}) or (b, 1, {S}, {S})")
+    raise ValueError(f"img_mask {tuple(m.shape)} is neither over the codes nor over the pixels: expected {sizes}")
+
+
 class DALLE(nn.Module):
     """DALL-E over VQGAN codes. ``forward(text, image, mask=None, return_loss=True)`` -> scalar loss."""
 
@@ -304,7 +323,8 @@ class DALLE(nn.Module):
     @torch.no_grad()
     def generate_images(self, text, *, clip=None, mask=None, filter_thres=None, temperature: float = 1.0, img=None,
                         num_init_img_tokens=None, top_k: int = 0, top_p: float = 1.0, use_cache: bool = True,
-                        return_codes: bool = False, use_graph=None, cond_scale: float = 1.0):
+                        return_codes: bool = False, use_graph=None, cond_scale: float = 1.0, img_mask=None,
+                        prefill_kept: bool = True, skip_tail: bool = True):
         """Sample 1024 image tokens per caption with the KV-cache decoder (hipGraph-replayed on MI355X)
         and decode them with ``self.vae`` to (b, 3, H, W) images in [0, 1] (codes if no VAE).
 
@@ -312,6 +332,12 @@ class DALLE(nn.Module):
         picture in [0, 1] is encoded with ``self.vae.get_codebook_indices``; a 2-D integer tensor is taken as image
         codes (works without a VAE). Its first ``num_init_img_tokens`` codes (default ``int(0.4375 *
         image_seq_len)``, as dalle-pytorch) are forced as the first image tokens and the rest is sampled.
+
+        ``img_mask`` (with ``img``, and without ``num_init_img_tokens``) inpaints instead: True / nonzero marks what is
+        regenerated, everything else keeps the picture's code. It is given over the codes -- (b, n) or (b, g, g), g the
+        code grid's side -- or over the pixels -- (b, S, S) or (b, 1, S, S), S the VAE's image size; a code cell is
+        regenerated if any of its pixels is marked. Masks differ per picture. ``prefill_kept`` / ``skip_tail``: see
+        ``DecodeEngine.generate``.
 
         ``cond_scale``: classifier-free guidance (for a model trained with ``null_cond_prob``). 1 is the plain path;
         any other value runs every picture's caption and the null caption side by side and samples from
@@ -324,7 +350,15 @@ class DALLE(nn.Module):
         if filter_thres is not None and not top_k:
             top_k = max(1, int((1 - filter_thres) * self.num_image_tokens))
         text_bos = self.prepare_text(text)
-        prime = None
+        prime = regen = None
+        if img_mask is not None:
+            if img is None:
+                raise ValueError("img_mask needs img: the picture whose unmasked codes are kept")
+            if num_init_img_tokens is not None:
+                raise ValueError("give either img_mask (inpainting) or num_init_img_tokens (a kept prefix), not both")
+            regen = code_mask(img_mask, text.shape[0], self.cfg.image_fmap_size,
+                              None if self.vae is None else getattr(self.vae, "image_size", None)).to(text.device)
+            num_init_img_tokens = 0  # the checks below then ask for a whole picture
         if img is not None:
             k = int(0.4375 * self.image_seq_len) if num_init_img_tokens is None else int(num_init_img_tokens)
             if not 0 <= k < self.image_seq_len:
@@ -340,12 +374,18 @@ class DALLE(nn.Module):
             if img.shape[1] < k:
                 raise ValueError(f"img holds {img.shape[1]} codes, fewer than the {k} to prime with")
             prime = img[:, :k].long().to(text.device)
+        if regen is not None:
+            if img.shape[1] != self.image_seq_len:
+                raise ValueError(f"inpainting needs all {self.image_seq_len} codes of the picture, got {img.shape[1]}")
+            prime = None
         slot = "_guided_decode_engine" if guided else "_decode_engine"
         eng = getattr(self, slot, None)
         if eng is None or eng.B != text.shape[0] or eng.device != text.device:
             eng = make_decode_engine(self, text.shape[0], device=text.device, **({"guided": True} if guided else {}))
             setattr(self, slot, eng)
         kw = {} if prime is None else {"prime": prime}
+        if regen is not None:
+            kw = {"image": img.long().to(text.device), "regen": regen, "prefill_kept": prefill_kept, "skip_tail": skip_tail}
         if guided:
             kw["cond_scale"] = float(cond_scale)
         codes = eng.generate(text_bos, temperature=temperature, top_k=top_k, top_p=top_p, use_graph=use_graph, **kw)

@@ -60,6 +60,35 @@ def _guidance_scale(guided: bool, cond_scale: Optional[float]) -> Optional[float
     return s
 
 
+def _check_inpaint(image, regen, batch: int, L: int, prime=None):
+    """The ``image`` / ``regen`` arguments of a ``generate`` call, checked: (batch, L) integer codes and a
+    (batch, L) bool mask (True = regenerate), both or neither, and not together with ``prime``."""
+    if image is None and regen is None:
+        return False
+    if image is None or regen is None:
+        raise ValueError("image and regen go together: the picture's codes and the mask of positions to regenerate")
+    if prime is not None:
+        raise ValueError("give either prime (a forced prefix) or image + regen (a mask), not both")
+    for name, t in (("image", image), ("regen", regen)):
+        if t.dim() != 2 or t.shape[0] != batch or t.shape[1] != L:
+            raise ValueError(f"{name} must be (batch {batch}, {L}), got {tuple(t.shape)}")
+    if image.dtype.is_floating_point or image.dtype == torch.bool:
+        raise ValueError("image must hold integer image codes")
+    if regen.dtype != torch.bool:
+        raise ValueError("regen must be a bool mask (True = regenerate)")
+    return True
+
+
+def _regen_window(regen: torch.Tensor):
+    """(k0, last): the smallest and the largest position any row regenerates (one host read); (L, -1) when no row
+    regenerates anything."""
+    L = regen.shape[1]
+    col = regen.any(0)
+    idx = torch.arange(L, device=regen.device)
+    k0, last = torch.stack([torch.where(col, idx, L).min(), torch.where(col, idx, -1).max()]).tolist()
+    return int(k0), int(last)
+
+
 class DecodeEngine:
     def __init__(self, model, batch_size: int, device=None, use_hip: Optional[bool] = None, skinny: bool = True,
                  partials: int = 2, fused_sampler: bool = True, guided: bool = False):
@@ -120,6 +149,9 @@ class DecodeEngine:
         # sample. Both live on the device, so one captured graph serves every prefix length, 0 included
         self.prime = torch.zeros(B, cfg.image_seq_len, dtype=torch.long, device=dev)
         self.n_prime = torch.zeros((), dtype=torch.int32, device=dev)
+        # inpainting: per picture, the positions that take prime's code as well (1 = keep); all zero otherwise. The
+        # captured step always reads it, so the same graph serves unprimed, prefix and masked calls
+        self.keep = torch.zeros(batch_size, cfg.image_seq_len, dtype=torch.uint8, device=dev)
         self.graph = None
         self._pf_graphs = {}  # captured caption prefills, by (rows, input buffer)
         self._pf_masks = {}   # contiguous (P, P) caption blocks of the layer patterns
@@ -155,6 +187,7 @@ class DecodeEngine:
         keeps pointing at the same buffers, so weight updates between calls are still seen)."""
         self.pos.zero_()
         self.n_prime.zero_()
+        self.keep.zero_()
         if self._refresh_weights:
             for p, w in self._w.values():
                 w.copy_(p.detach().reshape(w.shape))
@@ -334,7 +367,8 @@ class DecodeEngine:
             from ..ops.hip_ops import C
             C().sample_step(logits, int(self.top_k or 0), float(1.0 if self.top_p is None else self.top_p),
                             float(self.temperature), self.seed, self.pos, self.text_bos, self.codes, self.tok, self.Vt,
-                            prime=self.prime, n_prime=self.n_prime, **({"cond_scale": self.cond_scale} if self.guided else {}))
+                            prime=self.prime, n_prime=self.n_prime, keep=self.keep,
+                            **({"cond_scale": self.cond_scale} if self.guided else {}))
             self.pos.add_(1)
             return logits
         B, R = self.B, self.R
@@ -346,7 +380,8 @@ class DecodeEngine:
         p = self.pos.long()
         ci = p - (self.T - 1)
         idx = ci.clamp(0, self.cfg.image_seq_len - 1).view(1, 1).expand(B, 1)
-        nxt = torch.where((ci >= 0) & (ci < self.n_prime), self.prime[:B].gather(1, idx).view(B), nxt)
+        forced = (ci < self.n_prime) | (self.keep.gather(1, idx).view(B) != 0)
+        nxt = torch.where((ci >= 0) & (ci < self.cfg.image_seq_len) & forced, self.prime[:B].gather(1, idx).view(B), nxt)
         if self.guided:  # both halves take the picture's code
             nxt = torch.cat([nxt, nxt])
             idx = idx.repeat(2, 1)
@@ -396,6 +431,7 @@ class DecodeEngine:
         (None: no prefix). ``reset`` clears the count, so this goes after the last reset of a call."""
         if prime is None:
             self.n_prime.zero_()
+            self.keep.zero_()
             return
         L = self.cfg.image_seq_len
         if prime.dim() != 2 or prime.shape[0] != self.B or not 0 <= prime.shape[1] < L:  # B pictures: the sampler reads rows [0, B)
@@ -406,6 +442,25 @@ class DecodeEngine:
         if k:
             self.prime[:self.B, :k].copy_(prime)
         self.n_prime.fill_(k)
+
+    def set_keep(self, image: torch.Tensor, regen: torch.Tensor):
+        """Inpainting: the steps that follow keep ``image``'s code (B, image_seq_len) wherever ``regen`` (same shape,
+        bool) is False and sample the rest. Like ``set_prime``, it goes after the last reset of a call."""
+        _check_inpaint(image, regen, self.B, self.cfg.image_seq_len)
+        self.prime[:self.B].copy_(image)
+        self.keep.copy_(~regen)
+
+    def _warm_weights(self):
+        """Create the compute-dtype copies of every weight the prefill and the decode steps read, on the current
+        stream (a split engine calls this before its part streams fork: the parts share the copies, and a copy made
+        on one part's stream would be read by the other's without an ordering)."""
+        for f, g in self.pairs:
+            attn, ff = f.fn.fn.fn, g.fn.fn.fn
+            for p in (attn.to_qkv.weight, attn.to_out[0].weight, attn.to_out[0].bias, ff.net[0].weight, ff.net[0].bias,
+                      ff.net[3].weight, ff.net[3].bias):
+                self._wt(p)
+            self._scale(f)
+            self._scale(g)
 
     @torch.no_grad()
     def prefill(self, text_bos: torch.Tensor):
@@ -421,23 +476,32 @@ class DecodeEngine:
     # -- parallel prefill: the caption positions as ONE batched pass per layer -------------------------
     def _pf_ln_shift(self, ls, hist, x):
         """LN + cached token shift over all prefill positions at once: fills hist[:, :P] and returns the
-        shifted rows (the text shift takes channels [0, d/2) from the previous position)."""
+        shifted rows (the text shift takes channels [0, d/2) from the previous position; rows past the caption,
+        a pass that runs on over kept image codes, take the image shift of ``_ln_shift``: channels [0, d/4) from the
+        cell above, [d/4, d/2) from the cell to the left)."""
         pre = ls.fn
-        P = x.shape[1]
+        P, T, S = x.shape[1], self.T, self.S
         if self.use_hip and self.d in (256, 512, 1024, 2048):  # one kernel: LN, history rows, pushed shift
             from ..ops.hip_ops import C
             out = torch.empty(x.shape, dtype=self.cdt, device=x.device)
             C().prefill_ln_shift_(x, pre.norm.weight.detach(), pre.norm.bias.detach(), hist, out, bool(pre.fn.enabled),
-                                  float(pre.norm.eps))
+                                  float(pre.norm.eps), T, S)
             return out
         y = F.layer_norm(x, (self.d,), pre.norm.weight.detach(), pre.norm.bias.detach(), pre.norm.eps).to(self.cdt)
         hist[:, :P] = y
         if not pre.fn.enabled:
             return y
         out = y.clone()
-        h2 = self.d // 2
-        out[:, 1:, :h2] = y[:, :-1, :h2]
+        q, h2 = self.d // 4, self.d // 2
+        Tt = min(T, P)
+        out[:, 1:Tt, :h2] = y[:, :Tt - 1, :h2]
         out[:, 0, :h2] = 0
+        if P > T:  # image rows k = p - T
+            out[:, T:, :h2] = 0
+            if P > T + S:
+                out[:, T + S:, :q] = y[:, T:P - S, :q]
+            left = (torch.arange(P - T, device=x.device) % S != 0).view(1, -1, 1)
+            out[:, T:, q:h2] = torch.where(left, y[:, T - 1:P - 1, q:h2], torch.zeros((), dtype=y.dtype, device=x.device))
         return out
 
     def _pf_attn(self, li, ls, x):
@@ -454,14 +518,25 @@ class DecodeEngine:
             q = torch.empty(B * H, P, Dh, dtype=self.cdt, device=x.device)
             C().prefill_rope_(qkv, self.cos, self.sin, q, kc, vc, H, Dh ** -0.5)
             k, v = kc[:, :P], vc[:, :P]
-            sc = torch.bmm(q, k.transpose(1, 2), out_dtype=torch.float32)
-            mask = self._pf_mask(attn.attn_type, P, x.device)
-            if P <= 512:  # the kernel keeps a row's scores in registers (8 per lane)
+            if P <= min(self.T - 1, 512):  # the caption: one (P, P) block, a row's scores in registers (8 per lane)
+                sc = torch.bmm(q, k.transpose(1, 2), out_dtype=torch.float32)
                 pr = torch.empty(sc.shape, dtype=self.cdt, device=x.device)
-                C().prefill_softmax_(sc, mask, pr)
+                C().prefill_softmax_(sc, self._pf_mask(attn.attn_type, P, x.device), pr)
+                o = torch.bmm(pr, v)
             else:
-                pr = torch.softmax(sc.masked_fill_(~mask, float("-inf")), -1).to(self.cdt)
-            o = torch.bmm(pr, v)
+                # past the caption (kept image codes): blocks of queries against the keys up to the block's last
+                # (the rest is causally masked), so the fp32 scores stay at (rows, block, keys); each block reads its
+                # rows of the layer's whole static mask
+                mask = static_mask(self.geom, attn.attn_type, self.n, device=x.device)
+                Qb = P if P <= self.pf_dense_max else self.pf_query_block
+                o = torch.empty(B * H, P, Dh, dtype=self.cdt, device=x.device)
+                for q0 in range(0, P, Qb):
+                    Q = min(Qb, P - q0)
+                    Pk = q0 + Q
+                    sc = torch.bmm(q[:, q0:Pk], kc[:, :Pk].transpose(1, 2), out_dtype=torch.float32)
+                    pr = torch.empty(sc.shape, dtype=self.cdt, device=x.device)
+                    C().prefill_softmax_block_(sc, mask, pr, q0)
+                    torch.bmm(pr, vc[:, :Pk], out=o[:, q0:Pk])
             o = o.view(B, H, P, Dh).transpose(1, 2).reshape(B * P, H * Dh)
             return self._pf_linear(o, attn.to_out[0].weight, attn.to_out[0].bias).view(B, P, -1)
         qkv = F.linear(h, self._wt(attn.to_qkv.weight)).view(B, P, 3, H, Dh).permute(2, 0, 3, 1, 4).float()
@@ -530,8 +605,12 @@ class DecodeEngine:
         one = self.use_hip and self.share_text and self.B > 1 and bool(self.text_shared.item())
         return 1 if one else self.B
 
+    pf_dense_max = 512    # a prefill of up to this many positions takes its scores in one block
+    pf_query_block = 256  # queries per score block of a longer one (tests lower both to run the blocks on a small model)
+
     @torch.no_grad()
-    def prefill_parallel(self, text_bos: torch.Tensor, rows: Optional[int] = None, started: bool = False):
+    def prefill_parallel(self, text_bos: torch.Tensor, rows: Optional[int] = None, started: bool = False,
+                         kept: Optional[torch.Tensor] = None):
         """Positions 0..T-2 (BOS + caption) as one batched pass per layer instead of T-1 decode steps:
         fills the KV caches and LN histories exactly where the steps would, then leaves the engine at
         position T-1 (the first sampling step) -- at batch 64 on the reference model this replaces
@@ -541,9 +620,26 @@ class DecodeEngine:
         0's cache, ``text_shared``): the pass runs for row 0 alone, and the other rows get only what the decode
         steps read of their own: the LN history at position T-2 (the shift of the first step, at T-1).
         ``rows`` / ``started``: given by a caller that already ran ``_start`` and ``_pf_rows`` (a split
-        engine, which then launches the parts' passes on their streams with no host read in between)."""
+        engine, which then launches the parts' passes on their streams with no host read in between).
+
+        ``kept`` (B, k0) image codes, k0 >= 1: the pass runs on over the picture's first ``k0`` codes, which every row
+        keeps (inpainting) -- P = T - 1 + k0 positions, inputs the caption then codes 0 .. k0 - 2 -- and leaves the
+        engine at position P with code k0 - 1 as the next input, so the first decode step samples code k0. It
+        runs for all rows (the image keys / values are per row; the decode steps' shared text reads stay as they
+        are) and eagerly: a captured graph per distinct k0 would each hold a private pool."""
         if not started:
             self._start(text_bos)
+        if kept is not None and kept.shape[1] > 0:
+            k0 = kept.shape[1]
+            if kept.shape[0] != self.R:  # guided: both halves are fed the pictures' codes
+                kept = kept.repeat(self.R // kept.shape[0], 1)
+            kept = kept.to(self.text_bos.dtype) + self.Vt
+            P = self.T - 1 + k0
+            self._pf_body(self.R, P, torch.cat([self.text_bos, kept[:, :k0 - 1]], dim=1))
+            self.pos.fill_(P)
+            self.tok.copy_(kept[:, k0 - 1])
+            self.codes[:, :k0].copy_(kept - self.Vt)
+            return
         P = self.T - 1
         if rows is None:
             rows = self._pf_rows()
@@ -565,9 +661,10 @@ class DecodeEngine:
             self.pos.fill_(P)
         self.tok.copy_(self.text_bos[:, P])
 
-    def _pf_body(self, rows: int, P: int):
+    def _pf_body(self, rows: int, P: int, tokens: Optional[torch.Tensor] = None):
+        """``tokens`` (rows, P): the input ids of the P positions (default: the caption)."""
         W = self.model.to_logits[1].weight.detach()
-        x = F.embedding(self.text_bos[:rows, :P], W).float()
+        x = F.embedding(self.text_bos[:rows, :P] if tokens is None else tokens, W).float()
         if self.cfg.reversible:
             x1, x2 = x, x.clone()
             for li, (f, g) in enumerate(self.pairs):
@@ -585,7 +682,9 @@ class DecodeEngine:
     @torch.no_grad()
     def generate(self, text_bos: torch.Tensor, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
                  use_graph: Optional[bool] = None, seed: Optional[int] = None, parallel_prefill: Optional[bool] = None,
-                 prime: Optional[torch.Tensor] = None, cond_scale: Optional[float] = None) -> torch.Tensor:
+                 prime: Optional[torch.Tensor] = None, cond_scale: Optional[float] = None,
+                 image: Optional[torch.Tensor] = None, regen: Optional[torch.Tensor] = None, prefill_kept: bool = True,
+                 skip_tail: bool = True) -> torch.Tensor:
         """The caption prefill (one batched pass per layer, ``parallel_prefill``, default on; else T-1
         decode steps) then the 1024 sampled image tokens through one step function; on MI355X that step
         is a single hipGraph replayed per position. ``seed`` fixes the fused sampler's noise (default:
@@ -593,10 +692,24 @@ class DecodeEngine:
         forced to them (ordinary decode steps whose sample is replaced) and the rest sampled; the noise stays a
         function of (seed, position, row, token), so positions >= k draw what an unprimed call draws there.
         ``cond_scale`` (guided engines only): the guidance scale, a device scalar the captured step reads -- another
-        scale replays the same graph; 1 samples from the conditional rows' logits, 0 from the null caption's."""
+        scale replays the same graph; 1 samples from the conditional rows' logits, 0 from the null caption's.
+        ``image`` (B, image_seq_len) codes with ``regen`` (same shape, bool): inpainting. Every position is still
+        sampled given the caption and all earlier positions, but where ``regen`` is False the picture's code is kept
+        in place of the sample (per row; an all-True row is an ordinary unprimed row). Two savings, both on by
+        default: ``prefill_kept`` -- the codes before the first regenerated position of any row go through the
+        batched prefill together with the caption, not through decode steps; ``skip_tail`` -- no steps run after the
+        last regenerated position of any row. The noise of a regenerated position is the unmasked call's."""
+        masked = _check_inpaint(image, regen, self.B, self.cfg.image_seq_len, prime)
         s = _guidance_scale(self.guided, cond_scale)
         if s is not None:
             self.cond_scale.fill_(s)
+        k0, last = 0, self.cfg.image_seq_len - 1
+        if masked:
+            image, regen = image.to(self.device, torch.long), regen.to(self.device)
+            w0, w1 = _regen_window(regen)
+            if w1 < 0:  # nothing to regenerate
+                return image.clone()
+            k0, last = (w0 if prefill_kept else 0), (w1 if skip_tail else last)
         self.temperature, self.top_k, self.top_p = temperature, top_k, top_p
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
@@ -607,18 +720,24 @@ class DecodeEngine:
         self._start(text_bos)
         if use_graph:
             self._capture()
-        steps = self.n
         if parallel_prefill:
-            self.prefill_parallel(text_bos)
-            steps = self.n - (self.T - 1)
+            self.prefill_parallel(text_bos, kept=image[:, :k0] if k0 else None)
+            first = self.T - 1 + k0
         else:
             self._start(text_bos)
-        self.set_prime(prime)  # after the last reset (``_start`` above, or the one inside ``prefill_parallel``)
-        for _ in range(steps):
+            first = 0
+        # after the last reset (``_start`` above, or the one inside ``prefill_parallel``)
+        if masked:
+            self.set_keep(image, regen)
+        else:
+            self.set_prime(prime)
+        for _ in range(self.T + last - first):  # positions first .. T - 1 + last
             if use_graph:
                 self.graph.replay()
             else:
                 self._step()
+        if last + 1 < self.cfg.image_seq_len:  # the kept tail: no step ran for it
+            self.codes[:, last + 1:].copy_(image[:, last + 1:].repeat(self.R // self.B, 1))  # guided: both halves
         return self.codes[:self.B].clone()
 
     def _capture(self):
@@ -719,28 +838,34 @@ class SplitDecodeEngine:
             p.prefill(text_bos[i * b:(i + 1) * b])
 
     @torch.no_grad()
-    def prefill_parallel(self, text_bos: torch.Tensor):
+    def prefill_parallel(self, text_bos: torch.Tensor, kept: Optional[torch.Tensor] = None):
         """Every part's caption prefill, the parts' passes concurrently on the part streams (with distinct
         captions each pass is ~0.7 ms of mid-size GEMMs per layer for 32 rows: run one after the other
         they took 93 ms per generate call). The shared-caption flags are read on the host first, so no
-        synchronisation falls between the launches."""
+        synchronisation falls between the launches. ``kept`` (B, k0): the passes run on over the pictures' first
+        k0 codes (``DecodeEngine.prefill_parallel``), each part over its rows of them."""
         b = self.B // self.nparts
         slices = [text_bos[i * b:(i + 1) * b] for i in range(self.nparts)]
+        kepts = [None if kept is None else kept[i * b:(i + 1) * b] for i in range(self.nparts)]
         for p, t in zip(self.parts, slices):
             p._start(t)
         rows = [p._pf_rows() for p in self.parts]
         if not self.use_hip:
-            for p, t, r in zip(self.parts, slices, rows):
-                p.prefill_parallel(t, rows=r, started=True)
+            for p, t, r, kp in zip(self.parts, slices, rows, kepts):
+                p.prefill_parallel(t, rows=r, started=True, kept=kp)
             return
         if self._part_streams is None:
             self._part_streams = [torch.cuda.Stream() for _ in self.parts]
+        if kept is not None:
+            # an eager pass creates the shared bf16 weight copies where it first needs them: make them here, on the
+            # main stream, so that no part reads a copy another part's stream is still writing
+            self.parts[0]._warm_weights()
         main = torch.cuda.current_stream()
         for st in self._part_streams:
             st.wait_stream(main)
-        for p, t, r, st in zip(self.parts, slices, rows, self._part_streams):
+        for p, t, r, kp, st in zip(self.parts, slices, rows, kepts, self._part_streams):
             with torch.cuda.stream(st):
-                p.prefill_parallel(t, rows=r, started=True)
+                p.prefill_parallel(t, rows=r, started=True, kept=kp)
         for st in self._part_streams:
             main.wait_stream(st)
 
@@ -758,9 +883,22 @@ class SplitDecodeEngine:
     @torch.no_grad()
     def generate(self, text_bos: torch.Tensor, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
                  use_graph: Optional[bool] = None, seed: Optional[int] = None,
-                 prime: Optional[torch.Tensor] = None, cond_scale: Optional[float] = None) -> torch.Tensor:
+                 prime: Optional[torch.Tensor] = None, cond_scale: Optional[float] = None,
+                 image: Optional[torch.Tensor] = None, regen: Optional[torch.Tensor] = None, prefill_kept: bool = True,
+                 skip_tail: bool = True) -> torch.Tensor:
+        """``DecodeEngine.generate`` over the parts. ``image`` / ``regen`` (inpainting) are sliced per part; the
+        prefill over kept codes and the step window use the bounds over ALL rows, so the parts stay in step."""
         if prime is not None and (prime.dim() != 2 or prime.shape[0] != self.B):
             raise ValueError(f"prime must be (batch {self.B}, k), got {tuple(prime.shape)}")
+        L = self.parts[0].cfg.image_seq_len
+        masked = _check_inpaint(image, regen, self.B, L, prime)
+        k0, last = 0, L - 1
+        if masked:
+            image, regen = image.to(self.device, torch.long), regen.to(self.device)
+            w0, w1 = _regen_window(regen)
+            if w1 < 0:  # nothing to regenerate
+                return image.clone()
+            k0, last = (w0 if prefill_kept else 0), (w1 if skip_tail else last)
         s = _guidance_scale(self.guided, cond_scale)
         if s is not None:
             for p in self.parts:
@@ -771,21 +909,26 @@ class SplitDecodeEngine:
             p.temperature, p.top_k, p.top_p = temperature, top_k, top_p
             p.seed.fill_(int(seed) + i)
         use_graph = self.use_hip if use_graph is None else use_graph
-        n = self.parts[0].n
         self._start_all(text_bos)
         if use_graph:
             self._capture()
-        self.prefill_parallel(text_bos)
+        self.prefill_parallel(text_bos, kept=image[:, :k0] if k0 else None)
         b = self.B // self.nparts
         for i, p in enumerate(self.parts):  # after the parts' last reset (inside ``prefill_parallel``)
-            p.set_prime(None if prime is None else prime[i * b:(i + 1) * b])
-        steps = n - (self.parts[0].T - 1)
+            if masked:
+                p.set_keep(image[i * b:(i + 1) * b], regen[i * b:(i + 1) * b])
+            else:
+                p.set_prime(None if prime is None else prime[i * b:(i + 1) * b])
+        steps = last - k0 + 1  # image positions k0 .. last
         if use_graph:
             self.replay_steps(steps)
         else:
             for _ in range(steps):
                 for p in self.parts:
                     p._step()
+        if last + 1 < L:  # the kept tail: no step ran for it
+            for i, p in enumerate(self.parts):
+                p.codes[:, last + 1:].copy_(image[i * b:(i + 1) * b, last + 1:].repeat(p.R // p.B, 1))
         return self.codes.clone()
 
     def replay_steps(self, k: int):

@@ -65,25 +65,40 @@ def normalize_state_dict_keys(state_dict):
     return out
 
 
-def load_init_image(path: str, image_size: int) -> torch.Tensor:
-    """A picture file -> (3, S, S) float tensor in [0, 1]: short side resized to ``image_size``, centre crop."""
-    from PIL import Image
-
-    im = Image.open(path).convert("RGB")
+def _fit(im, image_size: int, resample):
+    """Short side resized to ``image_size``, centre crop (the framing ``--init-image`` and ``--mask`` share)."""
     w, h = im.size
     scale = image_size / min(w, h)
     w2, h2 = max(image_size, round(w * scale)), max(image_size, round(h * scale))
-    im = im.resize((w2, h2), Image.BICUBIC)
+    im = im.resize((w2, h2), resample)
     left, top = (w2 - image_size) // 2, (h2 - image_size) // 2
-    im = im.crop((left, top, left + image_size, top + image_size))
+    return im.crop((left, top, left + image_size, top + image_size))
+
+
+def load_init_image(path, image_size: int) -> torch.Tensor:
+    """A picture file -> (3, S, S) float tensor in [0, 1]: short side resized to ``image_size``, centre crop."""
+    from PIL import Image
+
+    im = _fit(Image.open(path).convert("RGB"), image_size, Image.BICUBIC)
     return torch.from_numpy(np.asarray(im, dtype=np.float32) / 255.0).permute(2, 0, 1).contiguous()
 
 
+def load_mask(path, image_size: int) -> torch.Tensor:
+    """An inpainting mask file -> (S, S) bool tensor over the pixels, True (white) = regenerate: framed like
+    ``load_init_image`` (the two files are expected to have the same size), nearest sampling."""
+    from PIL import Image
+
+    im = _fit(Image.open(path).convert("L"), image_size, Image.NEAREST)
+    return torch.from_numpy(np.asarray(im, dtype=np.uint8) >= 128)
+
+
 def generate(query, *, tokenizer, model, batch_size, n_iters, temperature, top_k, top_p, text_seq_len=256, device="cuda",
-             init_image=None, num_init_img_tokens=None, cond_scale=1.0):
+             init_image=None, num_init_img_tokens=None, cond_scale=1.0, mask=None):
     """``cond_scale``: classifier-free guidance scale (``DALLE.generate_images(cond_scale=...)``; 1 = off).
     ``init_image``: a (3, S, S) picture in [0, 1] (repeated over the batch) or (b, ...) images / codes, whose first
-    ``num_init_img_tokens`` VQGAN codes every sample starts from (``DALLE.generate_images(img=...)``)."""
+    ``num_init_img_tokens`` VQGAN codes every sample starts from (``DALLE.generate_images(img=...)``).
+    ``mask``: (S, S) over the pixels, or any layout ``DALLE.generate_images(img_mask=...)`` takes with the batch first:
+    inpainting, True = regenerate, the rest of ``init_image`` is kept."""
     ids = tokenizer(query, add_special_tokens=False, max_length=text_seq_len, truncation=True)['input_ids']
     input_ids = torch.full((text_seq_len,), 1, dtype=torch.long)
     input_ids[: len(ids)] = torch.tensor(ids, dtype=torch.long)
@@ -93,6 +108,10 @@ def generate(query, *, tokenizer, model, batch_size, n_iters, temperature, top_k
         if init_image.dim() == 3:
             init_image = init_image.unsqueeze(0).repeat(batch_size, 1, 1, 1)
         prime = dict(img=init_image.to(device), num_init_img_tokens=num_init_img_tokens)
+    if mask is not None:
+        if mask.dim() == 2 and mask.shape[0] == mask.shape[1]:
+            mask = mask.unsqueeze(0).repeat(batch_size, 1, 1)
+        prime["img_mask"] = mask.to(device)
     if cond_scale != 1.0:
         prime["cond_scale"] = cond_scale
     result = []
@@ -180,9 +199,16 @@ def main(argv=None):
                         help='[new] picture whose first VQGAN codes every sample starts from (image completion / variations)')
     parser.add_argument('--num-init-img-tokens', type=int, default=None,
                         help='[new] how many codes of --init-image to keep (default: 0.4375 of the image tokens)')
+    parser.add_argument('--mask', type=str, default=None,
+                        help='[new] inpainting mask for --init-image (white = regenerate, the rest of the picture is kept); '
+                             'resized and cropped like --init-image. Not together with --num-init-img-tokens')
     parser.add_argument('--cond-scale', type=float, default=1.0,
                         help='[new] classifier-free guidance scale (1 = off; for models trained with --null_cond_prob)')
     args = parser.parse_args(argv)
+    if args.mask and not args.init_image:
+        parser.error('--mask needs --init-image')
+    if args.mask and args.num_init_img_tokens is not None:
+        parser.error('--mask and --num-init-img-tokens exclude each other')
     torch.set_grad_enabled(False)  # inference only (the reference disabled grads at import time)
 
     queries = load_queries(args.queries)
@@ -216,6 +242,7 @@ def main(argv=None):
         print('[*] No --clip weights: clip_scores will be uniform')
 
     init_image = load_init_image(args.init_image, gan.image_size) if args.init_image else None
+    mask = load_mask(args.mask, gan.image_size) if args.mask else None
 
     os.makedirs(args.output_dir, exist_ok=True)
     print(f'[*] Saving results to `{args.output_dir}`')
@@ -227,7 +254,7 @@ def main(argv=None):
         images = generate(query, tokenizer=tokenizer, model=model, batch_size=args.batch_size, n_iters=args.n_iters,
                           temperature=args.temperature, top_k=args.top_k, top_p=args.top_p,
                           text_seq_len=model.model.text_seq_len, device=device, init_image=init_image,
-                          num_init_img_tokens=args.num_init_img_tokens, cond_scale=args.cond_scale)
+                          num_init_img_tokens=args.num_init_img_tokens, cond_scale=args.cond_scale, mask=mask)
         if clip_model is not None:
             from dalle_amd.models.clip import clip_scores as score_images
 

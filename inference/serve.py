@@ -14,10 +14,14 @@ counterpart for deployment. Requests are queued and a single GPU worker thread f
   padded size, so every shape's hipGraph is captured once and replayed for every later batch;
 * ``cond_scale`` other than 1 (classifier-free guidance) runs on a guided engine, cached per padded picture count
   beside the plain ones; the scale itself is a device scalar, so every scale replays the same graph;
+* ``init_image`` (with ``mask``: inpainting, white = regenerate; without: the first ``num_init_img_tokens`` codes are
+  kept) edits a picture: requests with and without pictures share a batch under the same sampling parameters -- a row
+  without a picture regenerates every position, which is the ordinary path, bit for bit;
 * codes are decoded by the VQGAN and returned as base64 PNGs together with per-request timings.
 
 Endpoints: ``POST /generate`` ``{"prompts": [...], "images_per_prompt": 1, "temperature": 1.0,
-"top_k": 256, "top_p": 1.0, "cond_scale": 1.0}``, ``GET /health``, ``GET /stats``. ``create_app`` builds the app around
+"top_k": 256, "top_p": 1.0, "cond_scale": 1.0, "init_image": <base64 PNG>, "mask": <base64 PNG>,
+"num_init_img_tokens": null}``, ``GET /health``, ``GET /stats``. ``create_app`` builds the app around
 an already-loaded model (tests, embedding into another service); ``main`` loads weights like
 ``run_inference.py`` and starts uvicorn.
 """
@@ -54,9 +58,16 @@ def _png_b64(img: np.ndarray) -> str:
     return base64.b64encode(buf.getvalue()).decode("ascii")
 
 
+def _b64_image(data: str, mode: str):
+    from PIL import Image
+
+    return Image.open(io.BytesIO(base64.b64decode(data))).convert(mode)
+
+
 class _Job:
-    def __init__(self, prompts: List[str], n: int, key: Tuple[float, int, float, float]):
+    def __init__(self, prompts: List[str], n: int, key: Tuple[float, int, float, float], image=None, regen=None):
         self.prompts, self.n, self.key = prompts, n, key
+        self.image, self.regen = image, regen  # (L,) codes and (L,) bool (True = regenerate), or None: no picture
         self.future: Future = Future()
         self.t_submit = time.perf_counter()
 
@@ -77,15 +88,23 @@ class BatchingGenerator:
         self.guided_engines: Dict[int, DecodeEngine] = {}  # classifier-free guidance, by padded picture count
         self.stats = {"requests": 0, "images": 0, "batches": 0, "gpu_seconds": 0.0}
         self._held: List[_Job] = []  # popped while batching but with other sampling parameters
+        self._vae_lock = threading.Lock()  # pictures are encoded in the submitting thread
         self._thread = threading.Thread(target=self._loop, name="dalle-serve-worker", daemon=True)
         self._thread.start()
 
     # -- API ------------------------------------------------------------------------------------
     def submit(self, prompts: List[str], images_per_prompt: int = 1, temperature: float = 1.0, top_k: int = 0,
-               top_p: float = 1.0, cond_scale: float = 1.0) -> Future:
+               top_p: float = 1.0, cond_scale: float = 1.0, init_image=None, mask=None, num_init_img_tokens=None) -> Future:
+        """``init_image``: a base64 PNG (encoded by the model's VQGAN) or the picture's codes (a sequence of
+        image_seq_len integers; works without a VAE). ``mask``: a base64 PNG (white = regenerate, framed like the
+        picture) or an array over the codes / pixels (``dalle_amd.models.dalle.code_mask``). Without a mask the first
+        ``num_init_img_tokens`` codes (default 0.4375 of them) are kept. The picture applies to every image of the
+        request."""
         if cond_scale < 0:
             raise ValueError("cond_scale must be >= 0")
-        job = _Job(list(prompts), int(images_per_prompt), (float(temperature), int(top_k), float(top_p), float(cond_scale)))
+        image, regen = self._picture(init_image, mask, num_init_img_tokens)
+        job = _Job(list(prompts), int(images_per_prompt), (float(temperature), int(top_k), float(top_p), float(cond_scale)),
+                   image, regen)
         if not job.prompts or job.n < 1:
             raise ValueError("need at least one prompt and images_per_prompt >= 1")
         if job.images > self.max_batch:
@@ -96,6 +115,46 @@ class BatchingGenerator:
     def close(self):
         self.q.put(None)
         self._thread.join(timeout=60)
+
+    def _picture(self, init_image, mask, num_init_img_tokens):
+        """A request's picture arguments -> ((L,) codes, (L,) bool regenerate mask) on the host, or (None, None)."""
+        from dalle_amd.models.dalle import code_mask
+
+        L, g, vae = self.model.image_seq_len, self.model.cfg.image_fmap_size, self.model.vae
+        if init_image is None:
+            if mask is not None or num_init_img_tokens is not None:
+                raise ValueError("mask and num_init_img_tokens need init_image")
+            return None, None
+        if mask is not None and num_init_img_tokens is not None:
+            raise ValueError("give either mask (inpainting) or num_init_img_tokens (a kept prefix), not both")
+        size = None if vae is None else getattr(vae, "image_size", None)
+        if isinstance(init_image, str):
+            if vae is None:
+                raise ValueError("a picture file needs a VAE to encode it; pass the picture's codes instead")
+            from run_inference import load_init_image
+
+            pic = load_init_image(io.BytesIO(base64.b64decode(init_image)), size)
+            with self._vae_lock:
+                image = vae.get_codebook_indices(pic.unsqueeze(0).to(self.device))[0].long().cpu()
+        else:
+            image = torch.as_tensor(init_image).reshape(-1)
+            if image.dtype.is_floating_point or image.dtype == torch.bool:
+                raise ValueError("init_image codes must be integers")
+            image = image.long().cpu()
+        if image.numel() != L:
+            raise ValueError(f"init_image must give {L} image codes, got {image.numel()}")
+        if mask is None:
+            k = int(0.4375 * L) if num_init_img_tokens is None else int(num_init_img_tokens)
+            if not 0 <= k < L:
+                raise ValueError(f"num_init_img_tokens must be in [0, {L}), got {k}")
+            return image, torch.arange(L) >= k
+        if isinstance(mask, str):
+            if size is None:
+                raise ValueError("a mask file is over the pixels and needs a VAE; pass a mask over the codes instead")
+            from run_inference import load_mask
+
+            mask = load_mask(io.BytesIO(base64.b64decode(mask)), size)
+        return image, code_mask(torch.as_tensor(mask).unsqueeze(0), 1, g, size)[0].cpu()
 
     # -- worker ---------------------------------------------------------------------------------
     def _next(self, timeout: Optional[float], held: bool = True) -> Optional[_Job]:
@@ -179,11 +238,25 @@ class BatchingGenerator:
         if eng is None:
             eng = cache[padded] = make_decode_engine(self.model, padded, device=self.device, **({"guided": True} if guided else {}))
         kw = {"cond_scale": cond_scale} if guided else {}
+        if any(job.image is not None for job in batch):
+            # one mask per row: a row without a picture regenerates everything (the ordinary path); the padded rows
+            # copy the last row's picture and mask
+            L = self.model.image_seq_len
+            image, regen = torch.zeros(padded, L, dtype=torch.long), torch.ones(padded, L, dtype=torch.bool)
+            off = 0
+            for job in batch:
+                if job.image is not None:
+                    image[off:off + job.images], regen[off:off + job.images] = job.image, job.regen
+                off += job.images
+            image[n:], regen[n:] = image[n - 1], regen[n - 1]
+            kw.update(image=image.to(self.device), regen=regen.to(self.device))
         t0 = time.perf_counter()
         codes = eng.generate(self.model.prepare_text(ids), temperature=temperature, top_k=top_k, top_p=top_p, **kw)[:n]
         imgs = self.model.vae.decode(codes) if self.model.vae is not None else None
         if self.device.type == "cuda":
-            torch.cuda.synchronize(self.device)
+            # this worker's stream only (the engines join their part streams into it): a device-wide synchronize is
+            # refused while another generator's thread captures a graph on the same GPU, and invalidates that capture
+            torch.cuda.current_stream(self.device).synchronize()
         gpu_s = time.perf_counter() - t0
         arr = imgs.permute(0, 2, 3, 1).float().cpu().numpy() if imgs is not None else None
         self.stats["batches"] += 1
@@ -238,13 +311,14 @@ class MultiDeviceGenerator:
         return tot
 
     def submit(self, prompts: List[str], images_per_prompt: int = 1, temperature: float = 1.0, top_k: int = 0,
-               top_p: float = 1.0, cond_scale: float = 1.0) -> Future:
+               top_p: float = 1.0, cond_scale: float = 1.0, init_image=None, mask=None, num_init_img_tokens=None) -> Future:
         n = len(prompts) * int(images_per_prompt)
         with self._lock:
             i = min(range(len(self.gens)), key=lambda k: (self._inflight[k], k))
             self._inflight[i] += n
         try:
-            fut = self.gens[i].submit(prompts, images_per_prompt, temperature, top_k, top_p, cond_scale)
+            fut = self.gens[i].submit(prompts, images_per_prompt, temperature, top_k, top_p, cond_scale, init_image, mask,
+                                      num_init_img_tokens)
         except Exception:
             with self._lock:
                 self._inflight[i] -= n
@@ -282,6 +356,9 @@ try:  # the HTTP layer is optional: BatchingGenerator works without fastapi / py
         top_k: int = Field(0, ge=0)
         top_p: float = Field(1.0, gt=0.0, le=1.0)
         cond_scale: float = Field(1.0, ge=0.0)
+        init_image: Optional[str] = None  # base64 PNG: the picture to edit
+        mask: Optional[str] = None  # base64 PNG, white = regenerate (needs init_image)
+        num_init_img_tokens: Optional[int] = Field(None, ge=0)  # without a mask: how many leading codes to keep
 except ImportError:  # pragma: no cover
     GenerateRequest = None
 
@@ -306,7 +383,8 @@ def create_app(gen):
     @app.post("/generate")
     def generate(req: GenerateRequest):
         try:
-            fut = gen.submit(req.prompts, req.images_per_prompt, req.temperature, req.top_k, req.top_p, req.cond_scale)
+            fut = gen.submit(req.prompts, req.images_per_prompt, req.temperature, req.top_k, req.top_p, req.cond_scale,
+                             req.init_image, req.mask, req.num_init_img_tokens)
         except ValueError as e:
             raise HTTPException(status_code=400, detail=str(e))
         return fut.result()
