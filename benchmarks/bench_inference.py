@@ -48,6 +48,14 @@ def main():
                     help="N rounds over the generation modes, alternating (sampling only, no VAE decode): full; 448 forced "
                          "codes as decode steps; the same as a suffix mask through the batched prefill; --inpaint-rows "
                          "(default 8:24) with both savings, with skip_tail only, with neither. Prints medians and spread")
+    ap.add_argument("--row-params", action="store_true",
+                    help="per-picture sampling parameters: the call goes through a row-parameter engine "
+                         "(DecodeEngine(row_params=True)) with uniform tables (--top-k for every picture)")
+    ap.add_argument("--row-mix", action="store_true",
+                    help="with --row-params: the first half of the pictures top-k (--top-k), the second half nucleus 0.9")
+    ap.add_argument("--row-ab", type=int, default=0, metavar="N",
+                    help="N rounds, alternating (sampling only, no VAE decode): the plain engine's scalar call; a row-parameter "
+                         "engine with uniform tables; the same with the --row-mix tables. Prints medians and spread")
     ap.add_argument("--profile-steps", type=int, default=0,
                     help="batched caption prefill + N image-position decode steps (graph replays unless --no-graph), "
                          "then exit (rocprof)")
@@ -79,19 +87,26 @@ def main():
     if args.inpaint_rows:
         gen_kw.update(img=picture, img_mask=rows_mask(args.inpaint_rows), prefill_kept=not args.no_prefill_kept,
                       skip_tail=not args.no_skip_tail)
-    eng = make_decode_engine(model, args.batch, device=dev, **({"guided": True} if guided else {}))
+    half = args.batch // 2
+    uniform = {"top_k": [args.top_k] * args.batch}
+    mixed = {"top_k": [args.top_k] * half + [0] * (args.batch - half), "top_p": [1.0] * half + [0.9] * (args.batch - half)}
+    samp = {"top_k": args.top_k}
+    if args.row_params:
+        samp = mixed if args.row_mix else uniform
+    slot = ("_guided_row_decode_engine" if guided else "_row_decode_engine") if args.row_params else (
+        "_guided_decode_engine" if guided else "_decode_engine")
+    eng = make_decode_engine(model, args.batch, device=dev, **({"guided": True} if guided else {}),
+                             **({"row_params": True} if args.row_params else {}))
+    setattr(model, slot, eng)
     if guided:
-        model._guided_decode_engine = eng
         for e in getattr(eng, "parts", [eng]):
             e.share_src = not args.no_share_src
-    else:
-        model._decode_engine = eng
     parts = getattr(eng, "nparts", 1)
     tb = model.prepare_text(text)
     prefill = getattr(eng, "prefill_parallel", eng.prefill)
     # warm-up generate (captures the step graph)
     t = time.perf_counter()
-    model.generate_images(text, top_k=args.top_k, use_graph=use_graph, **gen_kw)
+    model.generate_images(text, **samp, use_graph=use_graph, **gen_kw)
     torch.cuda.synchronize()
     print(f"# warm-up generate done: {time.perf_counter() - t:.2f}s", file=sys.stderr, flush=True)
     t = time.perf_counter()
@@ -99,6 +114,29 @@ def main():
     torch.cuda.synchronize()
     print(f"# batched prefill of {cfg.text_len} caption positions: {(time.perf_counter() - t) * 1e3:.1f} ms", file=sys.stderr,
           flush=True)
+    if args.row_ab:
+        base = {"cond_scale": args.cond_scale} if guided else {}
+        variants = [("plain engine, scalar call", {"top_k": args.top_k}), ("row engine, uniform tables", uniform),
+                    ("row engine, half top-k / half nucleus 0.9", mixed)]
+        times = {name: [] for name, _ in variants}
+        for rnd in range(args.row_ab + 1):  # round 0 is the warm-up of every variant (engines built, graphs captured)
+            for name, kw in variants:
+                torch.cuda.synchronize()
+                t = time.perf_counter()
+                model.generate_images(text, use_graph=use_graph, return_codes=True, **base, **kw)
+                torch.cuda.synchronize()
+                if rnd:
+                    times[name].append(time.perf_counter() - t)
+            print(f"# round {rnd} done", file=sys.stderr, flush=True)
+        res = {}
+        for name, ts in times.items():
+            ts = sorted(ts)
+            res[name] = {"median_s": round(ts[len(ts) // 2], 4), "min_s": round(ts[0], 4), "max_s": round(ts[-1], 4),
+                         "calls": len(ts)}
+        print(json.dumps({"metric": "sampling parameters per picture, seconds per call (sampling only, alternating rounds)",
+                          "batch": args.batch, "model": args.model, "top_k": args.top_k, "decode_parts": parts,
+                          "graph": use_graph, "variants": res}), flush=True)
+        return
     if args.inpaint_ab:
         k = int(0.4375 * L)
         band = rows_mask(args.inpaint_rows or f"{S // 4}:{3 * S // 4}")
@@ -141,20 +179,20 @@ def main():
         return
     # one more untimed generate: the first one after the standalone prefill above runs ~0.3 s slow
     # (profiles/r3_decode_partials_cols.txt), which is not the steady-state rate
-    model.generate_images(text, top_k=args.top_k, use_graph=use_graph, **gen_kw)
+    model.generate_images(text, **samp, use_graph=use_graph, **gen_kw)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(args.iters):
-        out = model.generate_images(text, top_k=args.top_k, use_graph=use_graph, **gen_kw)
+        out = model.generate_images(text, **samp, use_graph=use_graph, **gen_kw)
         torch.cuda.synchronize()
         print(f"# generate {i}: {time.perf_counter() - t0:.2f}s", file=sys.stderr, flush=True)
     el = (time.perf_counter() - t0) / args.iters
     # sampling alone (no VAE): batched caption prefill + 1024 decode steps, per sampled image token
     t2 = time.perf_counter()
-    model.generate_images(text, top_k=args.top_k, use_graph=use_graph, return_codes=True, **gen_kw)
+    model.generate_images(text, **samp, use_graph=use_graph, return_codes=True, **gen_kw)
     torch.cuda.synchronize()
     codes_s = time.perf_counter() - t2
-    eng = model._guided_decode_engine if guided else model._decode_engine
+    eng = getattr(model, slot)
     # decode-only timing: 256 image positions right after the batched caption prefill (every step
     # reads the 256 text keys of each layer's cache plus its local image keys). 256, not 64: the two
     # chains' per-part graphs run free and the window ends on the later one (~19 ms per window,
@@ -180,6 +218,7 @@ def main():
                       "captions": "one repeated" if args.same_caption else "distinct per row",
                       "text_shared": [int(e.text_shared.item()) for e in getattr(eng, "parts", [eng])],
                       **({"cond_scale": args.cond_scale, "rows": 2 * args.batch, "share_src": not args.no_share_src} if guided else {}),
+                      **({"row_params": "mixed" if args.row_mix else "uniform"} if args.row_params else {}),
                       "data": "random-init weights, synthetic captions"}), flush=True)
 
 

@@ -1220,7 +1220,9 @@ void decode_attn_(Tensor q, Tensor kc, Tensor vc, Tensor out, Tensor pos, int64_
 Tensor sample_step(Tensor logits, int64_t top_k, double top_p, double temperature, Tensor seed, Tensor pos,
                    c10::optional<Tensor> text, c10::optional<Tensor> codes, c10::optional<Tensor> tok, int64_t vt,
                    c10::optional<Tensor> prime, c10::optional<Tensor> n_prime, c10::optional<Tensor> cond_scale,
-                   c10::optional<Tensor> keep) {
+                   c10::optional<Tensor> keep, c10::optional<Tensor> row_temperature, c10::optional<Tensor> row_top_k,
+                   c10::optional<Tensor> row_top_p, c10::optional<Tensor> row_seed, c10::optional<Tensor> noise_row,
+                   c10::optional<Tensor> row_cond_scale) {
   CHECK_IN(logits, torch::kFloat32); CHECK_IN(seed, torch::kInt64); CHECK_IN(pos, torch::kInt32);
   TORCH_CHECK(logits.dim() == 2 && logits.size(1) >= 1 && logits.size(1) <= 8192, "sample: logits must be (B, V <= 8192)");
   TORCH_CHECK(seed.numel() == 1 && pos.numel() == 1, "sample: seed / pos are device scalars");
@@ -1275,6 +1277,44 @@ Tensor sample_step(Tensor logits, int64_t top_k, double top_p, double temperatur
     TORCH_CHECK(keep->dim() == 2 && keep->size(0) == pictures && keep->size(1) == a.img_len,
                 "sample: keep must be (pictures, image_len)");
     a.keep = static_cast<const uint8_t*>(keep->data_ptr());
+  }
+  // per-picture sampling parameters: the four tables together (then the scalar top_k / top_p / temperature / seed are
+  // not read), noise_row optional (absent: arange), row_cond_scale exactly when guided
+  const bool rows = row_temperature.has_value();
+  TORCH_CHECK(rows == row_top_k.has_value() && rows == row_top_p.has_value() && rows == row_seed.has_value(),
+              "sample: give row_temperature, row_top_k, row_top_p and row_seed together");
+  TORCH_CHECK(rows || !noise_row.has_value(), "sample: noise_row needs the row parameter tables");
+  TORCH_CHECK(rows || !row_cond_scale.has_value(), "sample: row_cond_scale needs the row parameter tables");
+  Tensor noise_rows;  // keeps a default arange alive until the launch is queued
+  if (rows) {
+    const int pictures = a.cond_scale != nullptr ? a.b : B;
+    auto check_row = [&](const Tensor& t, torch::ScalarType dt, const char* name) {
+      TORCH_CHECK(t.is_cuda() && t.device() == logits.device(), "sample: ", name, " must be on the logits' device");
+      TORCH_CHECK(t.scalar_type() == dt, "sample: ", name, " has the wrong dtype");
+      TORCH_CHECK(t.is_contiguous(), "sample: ", name, " must be contiguous");
+      TORCH_CHECK(t.dim() == 1 && t.size(0) == pictures, "sample: ", name, " must be (pictures,) = (", pictures, ",)");
+    };
+    check_row(*row_temperature, torch::kFloat32, "row_temperature");
+    check_row(*row_top_k, torch::kInt32, "row_top_k");
+    check_row(*row_top_p, torch::kFloat32, "row_top_p");
+    check_row(*row_seed, torch::kInt64, "row_seed");
+    TORCH_CHECK(row_cond_scale.has_value() == (a.cond_scale != nullptr),
+                "sample: row_cond_scale goes with cond_scale (guided) and the row parameter tables, and only with them");
+    if (row_cond_scale.has_value()) {
+      check_row(*row_cond_scale, torch::kFloat32, "row_cond_scale");
+      a.row_cond_scale = row_cond_scale->data_ptr<float>();
+    }
+    if (noise_row.has_value()) {
+      check_row(*noise_row, torch::kInt32, "noise_row");
+      noise_rows = *noise_row;
+    } else {
+      noise_rows = torch::arange(pictures, logits.options().dtype(torch::kInt32));
+    }
+    a.row_temperature = row_temperature->data_ptr<float>();
+    a.row_top_k = row_top_k->data_ptr<int>();
+    a.row_top_p = row_top_p->data_ptr<float>();
+    a.row_seed = row_seed->data_ptr<int64_t>();
+    a.noise_row = noise_rows.data_ptr<int>();
   }
   auto out = torch::empty({a.cond_scale != nullptr ? a.b : B}, logits.options().dtype(torch::kInt64));  // guided: (b,)
   a.sampled = out.data_ptr<int64_t>();
@@ -1456,7 +1496,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("sample_step", &sample_step, py::arg("logits"), py::arg("top_k"), py::arg("top_p"), py::arg("temperature"),
         py::arg("seed"), py::arg("pos"), py::arg("text") = py::none(), py::arg("codes") = py::none(),
         py::arg("tok") = py::none(), py::arg("vt") = 0, py::arg("prime") = py::none(), py::arg("n_prime") = py::none(),
-        py::arg("cond_scale") = py::none(), py::arg("keep") = py::none());
+        py::arg("cond_scale") = py::none(), py::arg("keep") = py::none(), py::arg("row_temperature") = py::none(),
+        py::arg("row_top_k") = py::none(), py::arg("row_top_p") = py::none(), py::arg("row_seed") = py::none(),
+        py::arg("noise_row") = py::none(), py::arg("row_cond_scale") = py::none());
   m.def("lamb_grad_norm", &lamb_grad_norm);
   m.def("lamb_step", &lamb_step);
 }

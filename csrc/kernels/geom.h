@@ -102,6 +102,14 @@ struct SampleArgs {
   // workgroup r samples from u + *cond_scale * (c - u) of rows r / r + b and writes both rows' codes and tokens
   const float* cond_scale;  // device scalar
   int b;                    // pictures (guided only)
+  // per-picture sampling parameters (all null: off; else all given, row_cond_scale when guided). Workgroup r reads
+  // entry r of each in place of top_k / top_p / temperature / *seed / *cond_scale above
+  const float* row_temperature;  // (pictures,)
+  const int* row_top_k;          // (pictures,)
+  const float* row_top_p;        // (pictures,)
+  const int64_t* row_seed;       // (pictures,)
+  const int* noise_row;          // (pictures,) the row of the noise key (seed, position, row, token), 24 bits
+  const float* row_cond_scale;   // (pictures,), guided only
 };
 
 }  // namespace dalle

@@ -24,6 +24,10 @@
 // fp32 operations while loading, samples from m exactly as above (noise keyed by r) and writes the code and the next
 // input token of BOTH rows. The scale is a device scalar: one captured graph serves every scale. A second
 // instantiation of the kernel, so the unguided one keeps its code.
+// Row parameters (`ROWS`, a further pair of instantiations): workgroup r reads its temperature, top-k, top-p, seed,
+// noise row and (guided) scale from per-picture device tables in place of the launch arguments and device scalars, so
+// one batch mixes sampling settings and one captured graph serves every setting. Only where the scalars come from
+// changes; the noise key's row becomes noise_row[r] (24 bits), so a picture's noise no longer depends on its slot.
 #include "common.h"
 #include "geom.h"
 
@@ -83,7 +87,7 @@ __device__ __forceinline__ int wave_sum_int(int v) {
   return v;
 }
 
-template <bool GUIDED>
+template <bool GUIDED, bool ROWS>
 __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(SampleArgs a) {
   __shared__ uint64_t srt[SMP_VMAX];  // top-p: (key << 32 | ~index), 64 KB
   __shared__ int cntb[2][SMP_NW];
@@ -92,12 +96,31 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(SampleArgs a) {
   const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const float* lr = a.logits + (size_t)row * a.V;
 
+  // the row's sampling scalars: the launch arguments, or (ROWS) this picture's table entries -- loaded here, beside
+  // the logits, and made scalar: they are uniform over the workgroup and the branches below hold barriers
+  int top_k = a.top_k, nrow = row;
+  float top_p = a.top_p, temperature = a.temperature, rscale = 0.f;
+  uint64_t rseed = 0ull;
+  if (ROWS) {
+    const int rk = a.row_top_k[row], rn = a.noise_row[row];
+    const float rp = a.row_top_p[row], rt = a.row_temperature[row];
+    const uint64_t rs = (uint64_t)a.row_seed[row];
+    const float rc = GUIDED ? a.row_cond_scale[row] : 0.f;
+    top_k = __builtin_amdgcn_readfirstlane(rk);
+    nrow = __builtin_amdgcn_readfirstlane(rn) & 0xffffff;
+    top_p = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(rp)));
+    temperature = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(rt)));
+    rscale = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(rc)));
+    rseed = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(rs >> 32)) << 32) |
+            (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)rs);
+  }
+
   uint32_t key[SMP_VPT];
   if (GUIDED) {
     // both rows' (clamped) loads in flight together, then the mix: sub, mul, add each rounded on its own (no fma
     // contraction), so the result is bitwise the host's u + s * (c - u) in fp32
     const float* ur = a.logits + (size_t)(row + a.b) * a.V;
-    const float s = *a.cond_scale;
+    const float s = ROWS ? rscale : *a.cond_scale;
     float lc[SMP_VPT], lu[SMP_VPT];
 #pragma unroll
     for (int i = 0; i < SMP_VPT; ++i) lc[i] = lr[min(i * SMP_THREADS + tid, a.V - 1)];
@@ -123,7 +146,7 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(SampleArgs a) {
   // radix histograms' LDS atomics serialised on the few exponent bins that logits share. (Two bits per step --
   // three candidate counts per barrier -- measured slower at 256 and at 1024 threads.)
   uint32_t kth = 0u;
-  if (a.top_k > 0 && a.top_k < a.V) {
+  if (top_k > 0 && top_k < a.V) {
     uint32_t t = 0u;
     for (int bit = 31; bit >= 0; --bit) {
       const uint32_t cand = t | (1u << bit);
@@ -135,13 +158,13 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(SampleArgs a) {
       int tot = 0;
 #pragma unroll
       for (int w = 0; w < SMP_NW; ++w) tot += cntb[bit & 1][w];
-      if (tot >= a.top_k) t = cand;
+      if (tot >= top_k) t = cand;
     }
     kth = t;
   }
 
   // ---- top-p: compact the survivors, sort descending, cut at the exclusive-cumsum crossing ----
-  const bool nucleus = a.top_p < 1.0f;
+  const bool nucleus = top_p < 1.0f;
   int n_keep = 0;
   if (nucleus) {
     int mine = 0;
@@ -180,7 +203,7 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(SampleArgs a) {
     for (int j = c0; j < c1; ++j) part += __expf(key_float((uint32_t)(srt[j] >> 32)) - mx);
     float psum;
     float run = block_excl_scan(part, redf, psum);
-    const float limit = a.top_p * psum;
+    const float limit = top_p * psum;
     // kept = #{j : exclusive_cum(j) <= limit}; monotone, so each chunk counts its own
     int kept = 0;
     for (int j = c0; j < c1; ++j) {
@@ -198,13 +221,13 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(SampleArgs a) {
 
   // ---- Gumbel-max sample (argmax, ties -> smallest index) ----
   const int pos = *a.pos;
-  const uint64_t seed = (uint64_t)*a.seed;
-  const bool greedy = !(a.temperature > 1e-10f);
-  const float invt = greedy ? 1.0f : 1.0f / a.temperature;
+  const uint64_t seed = ROWS ? rseed : (uint64_t)*a.seed;
+  const bool greedy = !(temperature > 1e-10f);
+  const float invt = greedy ? 1.0f : 1.0f / temperature;
   float best = -INFINITY;
   int besti = 0x7fffffff;
   auto consider = [&](float l, int idx) {
-    const float s = greedy ? l : l * invt + gumbel(seed, pos, row, idx);
+    const float s = greedy ? l : l * invt + gumbel(seed, pos, nrow, idx);
     if (s > best || (s == best && idx < besti)) { best = s; besti = idx; }
   };
   if (nucleus) {
@@ -283,10 +306,18 @@ bool sample_step(const SampleArgs& a, hipStream_t st) {
   if (a.B < 1 || a.V < 1 || a.V > SMP_VMAX) return false;
   if (a.cond_scale != nullptr) {
     if (a.b < 1 || a.B != 2 * a.b) return false;
-    hipLaunchKernelGGL(sample_kernel<true>, dim3(a.b), dim3(SMP_THREADS), 0, st, a);
+    if (a.row_seed != nullptr) {
+      if (a.row_cond_scale == nullptr) return false;
+      hipLaunchKernelGGL((sample_kernel<true, true>), dim3(a.b), dim3(SMP_THREADS), 0, st, a);
+    } else {
+      hipLaunchKernelGGL((sample_kernel<true, false>), dim3(a.b), dim3(SMP_THREADS), 0, st, a);
+    }
     return true;
   }
-  hipLaunchKernelGGL(sample_kernel<false>, dim3(a.B), dim3(SMP_THREADS), 0, st, a);
+  if (a.row_seed != nullptr)
+    hipLaunchKernelGGL((sample_kernel<false, true>), dim3(a.B), dim3(SMP_THREADS), 0, st, a);
+  else
+    hipLaunchKernelGGL((sample_kernel<false, false>), dim3(a.B), dim3(SMP_THREADS), 0, st, a);
   return true;
 }
 

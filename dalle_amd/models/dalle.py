@@ -324,7 +324,7 @@ class DALLE(nn.Module):
     def generate_images(self, text, *, clip=None, mask=None, filter_thres=None, temperature: float = 1.0, img=None,
                         num_init_img_tokens=None, top_k: int = 0, top_p: float = 1.0, use_cache: bool = True,
                         return_codes: bool = False, use_graph=None, cond_scale: float = 1.0, img_mask=None,
-                        prefill_kept: bool = True, skip_tail: bool = True):
+                        prefill_kept: bool = True, skip_tail: bool = True, seed=None, noise_row=None):
         """Sample 1024 image tokens per caption with the KV-cache decoder (hipGraph-replayed on MI355X)
         and decode them with ``self.vae`` to (b, 3, H, W) images in [0, 1] (codes if no VAE).
 
@@ -341,13 +341,28 @@ class DALLE(nn.Module):
 
         ``cond_scale``: classifier-free guidance (for a model trained with ``null_cond_prob``). 1 is the plain path;
         any other value runs every picture's caption and the null caption side by side and samples from
-        ``null + (cond - null) * cond_scale``, on a guided engine cached beside the plain one."""
-        from .generation import make_decode_engine
+        ``null + (cond - null) * cond_scale``, on a guided engine cached beside the plain one.
 
-        if cond_scale < 0:
-            raise ValueError(f"cond_scale must be >= 0, got {cond_scale}")
-        guided = cond_scale != 1
-        if filter_thres is not None and not top_k:
+        ``seed`` fixes the sampler's noise (default: drawn from torch's global generator). ``temperature``, ``top_k``,
+        ``top_p``, ``cond_scale`` and ``seed`` may each hold one entry per picture (list, tuple or tensor), and
+        ``noise_row`` one row index of the noise key per picture (default 0 .. b - 1): any of these routes the call to a
+        row-parameter engine (``DecodeEngine(row_params=True)``), cached beside the two scalar ones, on which picture
+        ``j`` samples with its own entries and its noise depends on (seed[j], noise_row[j]) only, not on its slot. A
+        sequence of guidance scales is guided if any entry differs from 1. Codes are bitwise reproducible at the same
+        batch size and engine kind (the decode GEMMs round per batch shape)."""
+        from .generation import _is_rows, make_decode_engine
+
+        rows = noise_row is not None or any(_is_rows(x) for x in (temperature, top_k, top_p, cond_scale, seed))
+        if _is_rows(cond_scale):
+            scales = [float(v) for v in (cond_scale.tolist() if isinstance(cond_scale, torch.Tensor) else cond_scale)]
+            if any(not v >= 0 for v in scales):
+                raise ValueError(f"cond_scale must be >= 0, got {scales}")
+            guided = any(v != 1 for v in scales)
+        else:
+            if cond_scale < 0:
+                raise ValueError(f"cond_scale must be >= 0, got {cond_scale}")
+            guided = cond_scale != 1
+        if filter_thres is not None and not _is_rows(top_k) and not top_k:
             top_k = max(1, int((1 - filter_thres) * self.num_image_tokens))
         text_bos = self.prepare_text(text)
         prime = regen = None
@@ -379,15 +394,22 @@ class DALLE(nn.Module):
                 raise ValueError(f"inpainting needs all {self.image_seq_len} codes of the picture, got {img.shape[1]}")
             prime = None
         slot = "_guided_decode_engine" if guided else "_decode_engine"
+        if rows:
+            slot = "_guided_row_decode_engine" if guided else "_row_decode_engine"
         eng = getattr(self, slot, None)
         if eng is None or eng.B != text.shape[0] or eng.device != text.device:
-            eng = make_decode_engine(self, text.shape[0], device=text.device, **({"guided": True} if guided else {}))
+            eng = make_decode_engine(self, text.shape[0], device=text.device, **({"guided": True} if guided else {}),
+                                     **({"row_params": True} if rows else {}))
             setattr(self, slot, eng)
         kw = {} if prime is None else {"prime": prime}
         if regen is not None:
             kw = {"image": img.long().to(text.device), "regen": regen, "prefill_kept": prefill_kept, "skip_tail": skip_tail}
         if guided:
-            kw["cond_scale"] = float(cond_scale)
+            kw["cond_scale"] = cond_scale if rows else float(cond_scale)
+        if seed is not None:
+            kw["seed"] = seed if rows else int(seed)
+        if noise_row is not None:
+            kw["noise_row"] = noise_row
         codes = eng.generate(text_bos, temperature=temperature, top_k=top_k, top_p=top_p, use_graph=use_graph, **kw)
         if return_codes or self.vae is None:
             return codes

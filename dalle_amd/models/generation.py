@@ -11,9 +11,12 @@ The CPU path runs the same step with the reference ops (tests compare it against
 """
 from __future__ import annotations
 
+import contextlib
+import gc
 import math
 import os
 import threading
+import weakref
 from typing import List, Optional
 
 import torch
@@ -26,6 +29,24 @@ from .rotary import apply_rotary, rotary_tables
 # run one at a time, in thread-local capture mode: another thread's replays and allocations on its own
 # device neither break a capture nor are refused while it runs
 _CAPTURE_LOCK = threading.Lock()
+
+
+@contextlib.contextmanager
+def _capture_into(graph):
+    """Capture the body into ``graph`` (one capture at a time, thread-local mode). Dead Python cycles are collected
+    first and the collector is paused until the capture ends: torch collects before a capture only on request, and a
+    cycle that dies inside one while it holds another engine's captured graph releases that graph's memory pool from
+    the capturing thread, which the runtime refuses during a capture -- in a destructor, so the process aborts."""
+    with _CAPTURE_LOCK:
+        gc.collect()
+        paused = gc.isenabled()
+        gc.disable()
+        try:
+            with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+                yield
+        finally:
+            if paused:
+                gc.enable()
 
 
 def filter_logits(logits: torch.Tensor, top_k: int = 0, top_p: float = 1.0) -> torch.Tensor:
@@ -60,6 +81,90 @@ def _guidance_scale(guided: bool, cond_scale: Optional[float]) -> Optional[float
     return s
 
 
+def filter_logits_rows(logits: torch.Tensor, top_k_rows: torch.Tensor, top_p_rows: torch.Tensor) -> torch.Tensor:
+    """``filter_logits`` with one ``(top_k, top_p)`` pair per row of ``logits`` (rows, V), vectorised over the rows:
+    row ``r`` of the result is ``filter_logits(logits[r], top_k_rows[r], top_p_rows[r])`` (``top_k <= 0`` or ``>= V``
+    and ``top_p >= 1`` switch the respective filter off for that row)."""
+    V = logits.shape[-1]
+    k = top_k_rows.to(logits.device, torch.long).view(-1, 1)
+    p = top_p_rows.to(logits.device, logits.dtype).view(-1, 1)
+    kth = torch.sort(logits, descending=True, dim=-1).values.gather(-1, k.clamp(1, V) - 1)  # the k-th largest, per row
+    logits = logits.masked_fill((k > 0) & (logits < kth), float("-inf"))
+    sorted_logits, sorted_idx = torch.sort(logits, descending=True, dim=-1)
+    probs = torch.softmax(sorted_logits, dim=-1)
+    remove = (probs.cumsum(-1) - probs > p) & (p < 1.0)  # keep the token that crosses top_p
+    sorted_logits = sorted_logits.masked_fill(remove, float("-inf"))
+    return torch.full_like(logits, float("-inf")).scatter(-1, sorted_idx, sorted_logits)
+
+
+def _is_rows(x) -> bool:
+    """A per-picture sequence (list, tuple, array, tensor of one or more dimensions), as opposed to a scalar."""
+    if isinstance(x, torch.Tensor):
+        return x.dim() > 0
+    return isinstance(x, (list, tuple)) or (hasattr(x, "__len__") and not isinstance(x, (str, bytes)))
+
+
+def _scalars_only(**params):
+    """A plain engine's sampling arguments, checked: per-picture sequences need a row-parameter engine."""
+    for name, x in params.items():
+        if _is_rows(x):
+            raise ValueError(f"{name} is a per-picture sequence: that needs an engine built with row_params=True")
+    if params.get("noise_row") is not None:
+        raise ValueError("noise_row needs an engine built with row_params=True")
+
+
+def row_generator_seed(seed: int, noise_row: int) -> int:
+    """The torch step's noise of a row-parameter engine: row ``r`` draws from its own ``torch.Generator``, seeded at the
+    start of ``generate`` with ``(seed[r] * 2**24 + noise_row[r]) mod 2**63`` -- a function of the row's own two table
+    entries only, so its draws depend neither on its slot nor on its neighbours."""
+    return (int(seed) * (1 << 24) + int(noise_row)) % (1 << 63)
+
+
+def _row_tables(batch: int, guided: bool, temperature, top_k, top_p, seed, cond_scale, noise_row) -> dict:
+    """The sampling arguments of a row-parameter ``generate`` call, checked on the host and broadcast: CPU tensors of
+    ``batch`` entries each -- temperature fp32, top_k int32, top_p fp32, seed int64, noise_row int32 (default
+    ``arange``) and, guided, cond_scale fp32. Each argument is a scalar or holds ``batch`` entries."""
+    def row(x, name, default, conv):
+        if x is None:
+            x = default
+        if isinstance(x, torch.Tensor):
+            x = x.detach().cpu().tolist()
+        elif _is_rows(x):
+            x = [v.item() if isinstance(v, torch.Tensor) else v for v in x]
+        if not isinstance(x, list):
+            x = [x] * batch
+        if len(x) != batch:
+            raise ValueError(f"{name} must be a scalar or hold one entry per picture ({batch}), got {len(x)}")
+        return [conv(v) for v in x]
+
+    if not guided and cond_scale is not None:
+        raise ValueError("cond_scale needs an engine built with guided=True")
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    t = {"temperature": row(temperature, "temperature", 1.0, float),
+         "top_k": row(top_k, "top_k", 0, lambda v: min(max(int(v or 0), 0), 2 ** 31 - 1)),
+         "top_p": row(top_p, "top_p", 1.0, lambda v: 1.0 if v is None else float(v)),
+         "seed": row(seed, "seed", 0, int),
+         "noise_row": row(noise_row, "noise_row", list(range(batch)), int)}
+    if guided:
+        t["cond_scale"] = row(cond_scale, "cond_scale", 1.0, float)
+        for s in t["cond_scale"]:
+            if not s >= 0:
+                raise ValueError(f"cond_scale must be >= 0, got {s}")
+    for p in t["top_p"]:
+        if not math.isfinite(p):
+            raise ValueError(f"top_p must be finite, got {p}")
+    for s in t["seed"]:
+        if not -(2 ** 63) <= s < 2 ** 63:
+            raise ValueError(f"seed must fit 64 bits, got {s}")
+    for r in t["noise_row"]:
+        if not 0 <= r < 2 ** 24:
+            raise ValueError(f"noise_row must lie in [0, 2**24), got {r}")
+    dt = {"temperature": torch.float32, "top_k": torch.int32, "top_p": torch.float32, "seed": torch.int64,
+          "noise_row": torch.int32, "cond_scale": torch.float32}
+    return {k: torch.tensor(v, dtype=dt[k]) for k, v in t.items()}
+
+
 def _check_inpaint(image, regen, batch: int, L: int, prime=None):
     """The ``image`` / ``regen`` arguments of a ``generate`` call, checked: (batch, L) integer codes and a
     (batch, L) bool mask (True = regenerate), both or neither, and not together with ``prime``."""
@@ -91,8 +196,11 @@ def _regen_window(regen: torch.Tensor):
 
 class DecodeEngine:
     def __init__(self, model, batch_size: int, device=None, use_hip: Optional[bool] = None, skinny: bool = True,
-                 partials: int = 2, fused_sampler: bool = True, guided: bool = False):
-        """``guided``: classifier-free guidance. The engine then owns ``2 * batch_size`` rows -- the pictures' captions
+                 partials: int = 2, fused_sampler: bool = True, guided: bool = False, row_params: bool = False):
+        """``row_params``: per-picture sampling parameters. The engine then owns device tables of one temperature,
+        top-k, top-p, seed, noise row and (guided) guidance scale per picture, which its step always reads in place of
+        the scalars: ``generate`` takes a scalar or a sequence for each, and one captured graph serves every setting.
+        ``guided``: classifier-free guidance. The engine then owns ``2 * batch_size`` rows -- the pictures' captions
         on top, the null caption below -- and samples picture ``r`` from ``u + cond_scale * (c - u)`` of rows ``r`` /
         ``r + batch_size`` (in the fused sampler's one launch), feeding the chosen code back to both rows.
         ``skinny``: decode projections on the skinny MFMA GEMM with fused epilogues (when the shapes allow);
@@ -152,6 +260,16 @@ class DecodeEngine:
         # inpainting: per picture, the positions that take prime's code as well (1 = keep); all zero otherwise. The
         # captured step always reads it, so the same graph serves unprimed, prefix and masked calls
         self.keep = torch.zeros(batch_size, cfg.image_seq_len, dtype=torch.uint8, device=dev)
+        self.row_params = bool(row_params)
+        if self.row_params:
+            n = batch_size
+            self.row_temperature = torch.ones(n, dtype=torch.float32, device=dev)
+            self.row_top_k = torch.zeros(n, dtype=torch.int32, device=dev)
+            self.row_top_p = torch.ones(n, dtype=torch.float32, device=dev)
+            self.row_seed = torch.zeros(n, dtype=torch.int64, device=dev)
+            self.noise_row = torch.arange(n, dtype=torch.int32, device=dev)
+            self.row_cond_scale = torch.ones(n, dtype=torch.float32, device=dev) if self.guided else None
+            self._row_gens = None  # the torch step's per-row generators (seeded per generate call)
         self.graph = None
         self._pf_graphs = {}  # captured caption prefills, by (rows, input buffer)
         self._pf_masks = {}   # contiguous (P, P) caption blocks of the layer patterns
@@ -361,6 +479,8 @@ class DecodeEngine:
         """Graph body for ANY position: run position ``pos``; choose the next input token on device --
         the next caption token while ``pos + 1 < T`` (prefill), else the sampled image token -- and
         record the sample as image code ``pos - T + 1`` (prefill writes are overwritten later)."""
+        if self.row_params:
+            return self._step_rows()
         logits = self._forward_position()
         if self.fused_sampler and logits.dtype == torch.float32 and logits.shape[-1] <= 8192:
             # one HIP launch (csrc/kernels/sample.hip): filter + sample + codes / next-token bookkeeping
@@ -391,7 +511,64 @@ class DecodeEngine:
         self.pos.add_(1)
         return logits
 
+    def _step_rows(self):
+        """``_step`` of a row-parameter engine: the same step, every sampling scalar read from the per-picture tables."""
+        logits = self._forward_position()
+        if self.fused_sampler and logits.dtype == torch.float32 and logits.shape[-1] <= 8192:
+            from ..ops.hip_ops import C
+            C().sample_step(logits, 0, 1.0, 1.0, self.seed, self.pos, self.text_bos, self.codes, self.tok, self.Vt,
+                            prime=self.prime, n_prime=self.n_prime, keep=self.keep,
+                            row_temperature=self.row_temperature, row_top_k=self.row_top_k, row_top_p=self.row_top_p,
+                            row_seed=self.row_seed, noise_row=self.noise_row,
+                            **({"cond_scale": self.cond_scale, "row_cond_scale": self.row_cond_scale} if self.guided else {}))
+            self.pos.add_(1)
+            return logits
+        B = self.B
+        if self.guided:  # the sampler's mix, with the picture's own scale
+            c, u = logits[:B].float(), logits[B:].float()
+            logits = u + self.row_cond_scale.view(B, 1) * (c - u)
+        logits = filter_logits_rows(logits.float(), self.row_top_k, self.row_top_p)
+        # row r's uniforms from its own generator (``row_generator_seed``); greedy where the temperature is <= 1e-10
+        u = torch.stack([torch.rand(logits.shape[-1], generator=g) for g in self._row_gens]).clamp_(1e-20, 1.0).to(logits.device)
+        t = self.row_temperature.view(B, 1)
+        greedy = ~(t > 1e-10)
+        noisy = logits / torch.where(greedy, torch.ones_like(t), t) - torch.log(-torch.log(u))
+        nxt = torch.argmax(torch.where(greedy, logits, noisy), dim=-1)
+        self._book(nxt)
+        return logits
+
+    def _book(self, nxt: torch.Tensor):
+        """The torch step's bookkeeping for the (B,) samples: forced codes, ``codes``, the next input token, ``pos``."""
+        B, R = self.B, self.R
+        p = self.pos.long()
+        ci = p - (self.T - 1)
+        idx = ci.clamp(0, self.cfg.image_seq_len - 1).view(1, 1).expand(B, 1)
+        forced = (ci < self.n_prime) | (self.keep.gather(1, idx).view(B) != 0)
+        nxt = torch.where((ci >= 0) & (ci < self.cfg.image_seq_len) & forced, self.prime[:B].gather(1, idx).view(B), nxt)
+        if self.guided:  # both halves take the picture's code
+            nxt = torch.cat([nxt, nxt])
+            idx = idx.repeat(2, 1)
+        self.codes.scatter_(1, idx, nxt.view(R, 1))
+        nxt_text = self.text_bos.gather(1, (p + 1).clamp(max=self.T - 1).view(1, 1).expand(R, 1)).view(R)
+        self.tok.copy_(torch.where(p + 1 < self.T, nxt_text, nxt + self.Vt))
+        self.pos.add_(1)
+
     _image_step = _step
+
+    def _set_rows(self, tables: dict, lo: int = 0):
+        """Load this engine's pictures' entries ``[lo, lo + B)`` of the checked tables (``_row_tables``)."""
+        hi = lo + self.B
+        self.row_temperature.copy_(tables["temperature"][lo:hi])
+        self.row_top_k.copy_(tables["top_k"][lo:hi])
+        self.row_top_p.copy_(tables["top_p"][lo:hi])
+        self.row_seed.copy_(tables["seed"][lo:hi])
+        self.noise_row.copy_(tables["noise_row"][lo:hi])
+        if self.guided:
+            self.row_cond_scale.copy_(tables["cond_scale"][lo:hi])
+        self._row_gens = [torch.Generator().manual_seed(row_generator_seed(s, r))
+                          for s, r in zip(tables["seed"][lo:hi].tolist(), tables["noise_row"][lo:hi].tolist())]
+        self.temperature, self.top_k, self.top_p = 1.0, 0, 1.0  # the scalars are not read
+        self.seed.zero_()
 
     # -- public API ---------------------------------------------------------------------------------
     def _rows_text(self, text_bos: torch.Tensor) -> torch.Tensor:
@@ -651,7 +828,7 @@ class DecodeEngine:
                 if graph is None:
                     self._pf_body(rows, P)  # the result, and the libraries' warm-up for the capture
                     graph = torch.cuda.CUDAGraph()
-                    with _CAPTURE_LOCK, torch.cuda.graph(graph, capture_error_mode="thread_local"):
+                    with _capture_into(graph):
                         self._pf_body(rows, P)
                     self._pf_graphs[key] = graph
                 else:
@@ -684,7 +861,7 @@ class DecodeEngine:
                  use_graph: Optional[bool] = None, seed: Optional[int] = None, parallel_prefill: Optional[bool] = None,
                  prime: Optional[torch.Tensor] = None, cond_scale: Optional[float] = None,
                  image: Optional[torch.Tensor] = None, regen: Optional[torch.Tensor] = None, prefill_kept: bool = True,
-                 skip_tail: bool = True) -> torch.Tensor:
+                 skip_tail: bool = True, noise_row=None) -> torch.Tensor:
         """The caption prefill (one batched pass per layer, ``parallel_prefill``, default on; else T-1
         decode steps) then the 1024 sampled image tokens through one step function; on MI355X that step
         is a single hipGraph replayed per position. ``seed`` fixes the fused sampler's noise (default:
@@ -698,8 +875,23 @@ class DecodeEngine:
         in place of the sample (per row; an all-True row is an ordinary unprimed row). Two savings, both on by
         default: ``prefill_kept`` -- the codes before the first regenerated position of any row go through the
         batched prefill together with the caption, not through decode steps; ``skip_tail`` -- no steps run after the
-        last regenerated position of any row. The noise of a regenerated position is the unmasked call's."""
+        last regenerated position of any row. The noise of a regenerated position is the unmasked call's.
+        On a ``row_params`` engine ``temperature``, ``top_k``, ``top_p``, ``seed`` and (guided) ``cond_scale`` each take
+        a scalar or one entry per picture, and ``noise_row`` (default ``arange(B)``) names the row of each picture's
+        noise key: picture ``j`` samples with its own entries, its noise a function of (seed[j], position,
+        noise_row[j], token) -- not of its slot. All are checked on the host before anything is launched."""
         masked = _check_inpaint(image, regen, self.B, self.cfg.image_seq_len, prime)
+        tables = None
+        if self.row_params:
+            tables = _row_tables(self.B, self.guided, temperature, top_k, top_p, seed, cond_scale, noise_row)
+            temperature, top_k, top_p, seed, cond_scale = 1.0, 0, 1.0, 0, None
+            if use_graph and not self.fused_sampler:
+                raise ValueError("the torch sampling step of a row-parameter engine draws from host generators: no graph")
+            if use_graph is None:
+                use_graph = self.use_hip and self.fused_sampler
+        else:
+            _scalars_only(temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, cond_scale=cond_scale,
+                          noise_row=noise_row)
         s = _guidance_scale(self.guided, cond_scale)
         if s is not None:
             self.cond_scale.fill_(s)
@@ -714,6 +906,8 @@ class DecodeEngine:
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         self.seed.fill_(int(seed))
+        if tables is not None:
+            self._set_rows(tables)
         use_graph = self.use_hip if use_graph is None else use_graph
         if parallel_prefill is None:
             parallel_prefill = True
@@ -742,8 +936,8 @@ class DecodeEngine:
 
     def _capture(self):
         """Capture one image step into a hipGraph (warm-up on a side stream as torch requires)."""
-        if self.graph is not None and self._graph_cfg == (self.temperature, self.top_k, self.top_p):
-            return
+        if self.graph is not None and (self.row_params or self._graph_cfg == (self.temperature, self.top_k, self.top_p)):
+            return  # row parameters live in device tables: one capture serves every later call
         # warm-up on a side stream (allocator / library handles), then capture; the caller resets the
         # state (pos, tokens, caches) afterwards, so the warm-up steps leave no trace
         s = torch.cuda.Stream()
@@ -753,7 +947,7 @@ class DecodeEngine:
                 self._step()
         torch.cuda.current_stream().wait_stream(s)
         g = torch.cuda.CUDAGraph()
-        with _CAPTURE_LOCK, torch.cuda.graph(g, capture_error_mode="thread_local"):
+        with _capture_into(g):
             self._static_logits = self._step()
         self.graph = g
         self._graph_cfg = (self.temperature, self.top_k, self.top_p)
@@ -778,10 +972,10 @@ class _PartGraphs:
     (the ``graph`` of a :class:`SplitDecodeEngine`)."""
 
     def __init__(self, eng):
-        self.eng = eng
+        self.eng = weakref.ref(eng)  # not a cycle: a dropped engine frees its graphs at once, not in a later collection
 
     def replay(self):
-        self.eng.replay_steps(1)
+        self.eng().replay_steps(1)
 
 
 class SplitDecodeEngine:
@@ -797,14 +991,19 @@ class SplitDecodeEngine:
     parts. (One graph with the parts as parallel branches is launched node by node, ~2.5 ms of host time per
     ~3 ms step: profiles/r6_decode_replay_host.txt, 3.00-3.02 vs 3.05-3.11 ms per step.)"""
 
-    def __init__(self, model, batch_size: int, device=None, parts: int = 2, guided: bool = False):
-        """``guided``: every part is a guided engine over its slice of the pictures, with its own conditional and
+    def __init__(self, model, batch_size: int, device=None, parts: int = 2, guided: bool = False,
+                 row_params: bool = False):
+        """``row_params``: every part is a row-parameter engine and takes its slice of the caller's tables as they are
+        (no part index is added to the seeds: the table is the truth).
+        ``guided``: every part is a guided engine over its slice of the pictures, with its own conditional and
         null rows, so no part reads another's buffers."""
         if batch_size % parts:
             raise ValueError(f"batch {batch_size} is not divisible into {parts} parts")
         self.model, self.B, self.nparts = model, batch_size, parts
         self.guided = bool(guided)
-        self.parts = [DecodeEngine(model, batch_size // parts, device=device, guided=guided) for _ in range(parts)]
+        self.row_params = bool(row_params)
+        kw = {"row_params": True} if self.row_params else {}
+        self.parts = [DecodeEngine(model, batch_size // parts, device=device, guided=guided, **kw) for _ in range(parts)]
         for p in self.parts[1:]:
             p._w = self.parts[0]._w  # one bf16 copy of every weight, refreshed by part 0 only
             p._refresh_weights = False
@@ -856,7 +1055,7 @@ class SplitDecodeEngine:
             return
         if self._part_streams is None:
             self._part_streams = [torch.cuda.Stream() for _ in self.parts]
-        if kept is not None:
+        if kept is not None or self.row_params:
             # an eager pass creates the shared bf16 weight copies where it first needs them: make them here, on the
             # main stream, so that no part reads a copy another part's stream is still writing
             self.parts[0]._warm_weights()
@@ -870,7 +1069,8 @@ class SplitDecodeEngine:
             main.wait_stream(st)
 
     def _capture(self):
-        cfg = (self.parts[0].temperature, self.parts[0].top_k, self.parts[0].top_p)
+        # a row-parameter engine's capture is keyed on nothing: its parts read every setting from their tables
+        cfg = None if self.row_params else (self.parts[0].temperature, self.parts[0].top_k, self.parts[0].top_p)
         if self.graph is not None and self._graph_cfg == cfg:
             return
         for p in self.parts:
@@ -885,9 +1085,18 @@ class SplitDecodeEngine:
                  use_graph: Optional[bool] = None, seed: Optional[int] = None,
                  prime: Optional[torch.Tensor] = None, cond_scale: Optional[float] = None,
                  image: Optional[torch.Tensor] = None, regen: Optional[torch.Tensor] = None, prefill_kept: bool = True,
-                 skip_tail: bool = True) -> torch.Tensor:
+                 skip_tail: bool = True, noise_row=None) -> torch.Tensor:
         """``DecodeEngine.generate`` over the parts. ``image`` / ``regen`` (inpainting) are sliced per part; the
-        prefill over kept codes and the step window use the bounds over ALL rows, so the parts stay in step."""
+        prefill over kept codes and the step window use the bounds over ALL rows, so the parts stay in step. With
+        ``row_params`` every per-picture table (``noise_row`` included, default ``arange(B)`` over the whole batch) is
+        sliced per part as given."""
+        tables = None
+        if self.row_params:
+            tables = _row_tables(self.B, self.guided, temperature, top_k, top_p, seed, cond_scale, noise_row)
+            temperature, top_k, top_p, seed, cond_scale = 1.0, 0, 1.0, 0, None
+        else:
+            _scalars_only(temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, cond_scale=cond_scale,
+                          noise_row=noise_row)
         if prime is not None and (prime.dim() != 2 or prime.shape[0] != self.B):
             raise ValueError(f"prime must be (batch {self.B}, k), got {tuple(prime.shape)}")
         L = self.parts[0].cfg.image_seq_len
@@ -908,6 +1117,8 @@ class SplitDecodeEngine:
         for i, p in enumerate(self.parts):
             p.temperature, p.top_k, p.top_p = temperature, top_k, top_p
             p.seed.fill_(int(seed) + i)
+            if tables is not None:
+                p._set_rows(tables, i * p.B)
         use_graph = self.use_hip if use_graph is None else use_graph
         self._start_all(text_bos)
         if use_graph:
@@ -960,13 +1171,14 @@ def decode_parts(batch_size: int, device, parts: Optional[int] = None) -> int:
     return n if batch_size % n == 0 else 1
 
 
-def make_decode_engine(model, batch_size: int, device=None, guided: bool = False):
-    """``guided``: an engine for classifier-free guidance (two rows per picture). The split into parts is decided
+def make_decode_engine(model, batch_size: int, device=None, guided: bool = False, row_params: bool = False):
+    """``row_params``: an engine with per-picture sampling parameters (``DecodeEngine``).
+    ``guided``: an engine for classifier-free guidance (two rows per picture). The split into parts is decided
     on the row count; the skinny GEMM limit is 64 rows, so at most 32 guided pictures stay on that path."""
     device = device or next(model.parameters()).device
     parts = decode_parts(2 * batch_size if guided else batch_size, device)
     if parts > 1 and batch_size % parts == 0:
-        eng = SplitDecodeEngine(model, batch_size, device=device, parts=parts, guided=guided)
+        eng = SplitDecodeEngine(model, batch_size, device=device, parts=parts, guided=guided, row_params=row_params)
         if eng.use_hip:
             return eng
-    return DecodeEngine(model, batch_size, device=device, guided=guided)
+    return DecodeEngine(model, batch_size, device=device, guided=guided, row_params=row_params)

@@ -92,9 +92,17 @@ def load_mask(path, image_size: int) -> torch.Tensor:
     return torch.from_numpy(np.asarray(im, dtype=np.uint8) >= 128)
 
 
+def call_seed(seed: int, query_index: int, batch_index: int) -> int:
+    """``--seed N``: the sampler seed of generate call ``batch_index`` of query ``query_index`` (its position in the
+    queries file) is ``(N + 1000003 * query_index + batch_index) mod 2**62`` -- a function of the three numbers only, so
+    neither the device a query lands on nor the order the devices finish in changes what is written."""
+    return (int(seed) + 1000003 * int(query_index) + int(batch_index)) % (1 << 62)
+
+
 def generate(query, *, tokenizer, model, batch_size, n_iters, temperature, top_k, top_p, text_seq_len=256, device="cuda",
-             init_image=None, num_init_img_tokens=None, cond_scale=1.0, mask=None):
-    """``cond_scale``: classifier-free guidance scale (``DALLE.generate_images(cond_scale=...)``; 1 = off).
+             init_image=None, num_init_img_tokens=None, cond_scale=1.0, mask=None, seed=None, query_index=0):
+    """``seed``: call ``i`` of the ``n_iters`` samples with ``call_seed(seed, query_index, i)`` (None: unseeded, as before).
+    ``cond_scale``: classifier-free guidance scale (``DALLE.generate_images(cond_scale=...)``; 1 = off).
     ``init_image``: a (3, S, S) picture in [0, 1] (repeated over the batch) or (b, ...) images / codes, whose first
     ``num_init_img_tokens`` VQGAN codes every sample starts from (``DALLE.generate_images(img=...)``).
     ``mask``: (S, S) over the pixels, or any layout ``DALLE.generate_images(img_mask=...)`` takes with the batch first:
@@ -115,7 +123,9 @@ def generate(query, *, tokenizer, model, batch_size, n_iters, temperature, top_k
     if cond_scale != 1.0:
         prime["cond_scale"] = cond_scale
     result = []
-    for _ in range(n_iters):
+    for it in range(n_iters):
+        if seed is not None:
+            prime["seed"] = call_seed(seed, query_index, it)
         output = model.model.generate_images(input_ids, temperature=temperature, top_k=top_k, top_p=top_p, use_cache=True,
                                              **prime)
         output = output.permute(0, 2, 3, 1).float().cpu().numpy()
@@ -202,6 +212,10 @@ def main(argv=None):
     parser.add_argument('--mask', type=str, default=None,
                         help='[new] inpainting mask for --init-image (white = regenerate, the rest of the picture is kept); '
                              'resized and cropped like --init-image. Not together with --num-init-img-tokens')
+    parser.add_argument('--seed', type=int, default=None,
+                        help='[new] reproducible sampling: generate call i of query q (its line in --queries) uses the seed '
+                             '(N + 1000003 q + i) mod 2**62; two runs with the same --seed, batch size and devices kind '
+                             'write the same pickles')
     parser.add_argument('--cond-scale', type=float, default=1.0,
                         help='[new] classifier-free guidance scale (1 = off; for models trained with --null_cond_prob)')
     args = parser.parse_args(argv)
@@ -249,12 +263,14 @@ def main(argv=None):
     if len(devices) > 1:
         print(f'[*] {len(devices)} devices: {", ".join(devices)}')
 
-    def work(query, ctx):
+    def work(item, ctx):
+        query_index, query = item
         model, clip_model, device = ctx
         images = generate(query, tokenizer=tokenizer, model=model, batch_size=args.batch_size, n_iters=args.n_iters,
                           temperature=args.temperature, top_k=args.top_k, top_p=args.top_p,
                           text_seq_len=model.model.text_seq_len, device=device, init_image=init_image,
-                          num_init_img_tokens=args.num_init_img_tokens, cond_scale=args.cond_scale, mask=mask)
+                          num_init_img_tokens=args.num_init_img_tokens, cond_scale=args.cond_scale, mask=mask,
+                          seed=args.seed, query_index=query_index)
         if clip_model is not None:
             from dalle_amd.models.clip import clip_scores as score_images
 
@@ -265,7 +281,7 @@ def main(argv=None):
             outputs = {'query': query, 'temperature': args.temperature, 'images': images, 'clip_scores': clip_scores}
             pickle.dump(outputs, f)
 
-    run_queries(queries, list(zip(models, clip_models, devices)), work, device_of=lambda ctx: ctx[2])
+    run_queries(list(enumerate(queries)), list(zip(models, clip_models, devices)), work, device_of=lambda ctx: ctx[2])
 
 
 if __name__ == '__main__':

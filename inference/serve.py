@@ -17,11 +17,20 @@ counterpart for deployment. Requests are queued and a single GPU worker thread f
 * ``init_image`` (with ``mask``: inpainting, white = regenerate; without: the first ``num_init_img_tokens`` codes are
   kept) edits a picture: requests with and without pictures share a batch under the same sampling parameters -- a row
   without a picture regenerates every position, which is the ordinary path, bit for bit;
+* ``seed`` (an int64) makes a request replayable: image ``i`` of the request samples with the noise key
+  ``(seed, noise_row = i)`` on a row-parameter engine (``DecodeEngine(row_params=True)``), whatever its batch slot and
+  neighbours, and the response echoes the seed. Codes are bitwise reproducible at the same padded batch size and engine
+  kind (the decode GEMMs round per batch shape). Without ``--mix-params`` a seeded request batches only with seeded
+  requests of the same parameters, and a request without a seed takes the plain path (its response's seed is null:
+  that path's noise is keyed by the batch slot and cannot be replayed per picture);
+* ``--mix-params`` (``mix_params=True``; off by default): the batching key shrinks to "guided or not". Every batch
+  runs on a row-parameter engine with one temperature / top-k / top-p / guidance scale / seed per picture, so requests
+  with different settings share a batch, and a request without a seed gets one drawn at ``submit``;
 * codes are decoded by the VQGAN and returned as base64 PNGs together with per-request timings.
 
 Endpoints: ``POST /generate`` ``{"prompts": [...], "images_per_prompt": 1, "temperature": 1.0,
 "top_k": 256, "top_p": 1.0, "cond_scale": 1.0, "init_image": <base64 PNG>, "mask": <base64 PNG>,
-"num_init_img_tokens": null}``, ``GET /health``, ``GET /stats``. ``create_app`` builds the app around
+"num_init_img_tokens": null, "seed": null}``, ``GET /health``, ``GET /stats``. ``create_app`` builds the app around
 an already-loaded model (tests, embedding into another service); ``main`` loads weights like
 ``run_inference.py`` and starts uvicorn.
 """
@@ -33,6 +42,7 @@ import copy
 import io
 import os
 import queue
+import secrets
 import sys
 import threading
 import time
@@ -65,8 +75,11 @@ def _b64_image(data: str, mode: str):
 
 
 class _Job:
-    def __init__(self, prompts: List[str], n: int, key: Tuple[float, int, float, float], image=None, regen=None):
+    def __init__(self, prompts: List[str], n: int, key: tuple, image=None, regen=None, params=None, seed=None):
         self.prompts, self.n, self.key = prompts, n, key
+        # params (temperature, top_k, top_p, cond_scale) and the seed of a job that runs on a row-parameter engine
+        # (``rows``); a plain job's parameters are its key
+        self.params, self.seed, self.rows = params, seed, params is not None
         self.image, self.regen = image, regen  # (L,) codes and (L,) bool (True = regenerate), or None: no picture
         self.future: Future = Future()
         self.t_submit = time.perf_counter()
@@ -79,13 +92,17 @@ class _Job:
 class BatchingGenerator:
     """Owns the model on one device; ``submit`` is thread-safe, all GPU work happens in one thread."""
 
-    def __init__(self, model, tokenizer, device, max_batch: int = 64, batch_window_ms: float = 20.0):
+    def __init__(self, model, tokenizer, device, max_batch: int = 64, batch_window_ms: float = 20.0,
+                 mix_params: bool = False):
         self.model, self.tokenizer, self.device = model, tokenizer, torch.device(device)
+        self.mix_params = bool(mix_params)
         self.max_batch = max(1, int(max_batch))
         self.window = batch_window_ms / 1000.0
         self.q: "queue.Queue[Optional[_Job]]" = queue.Queue()
         self.engines: Dict[int, DecodeEngine] = {}
         self.guided_engines: Dict[int, DecodeEngine] = {}  # classifier-free guidance, by padded picture count
+        self.row_engines: Dict[int, DecodeEngine] = {}  # per-picture sampling parameters (seeded or mixed batches)
+        self.guided_row_engines: Dict[int, DecodeEngine] = {}
         self.stats = {"requests": 0, "images": 0, "batches": 0, "gpu_seconds": 0.0}
         self._held: List[_Job] = []  # popped while batching but with other sampling parameters
         self._vae_lock = threading.Lock()  # pictures are encoded in the submitting thread
@@ -94,8 +111,10 @@ class BatchingGenerator:
 
     # -- API ------------------------------------------------------------------------------------
     def submit(self, prompts: List[str], images_per_prompt: int = 1, temperature: float = 1.0, top_k: int = 0,
-               top_p: float = 1.0, cond_scale: float = 1.0, init_image=None, mask=None, num_init_img_tokens=None) -> Future:
-        """``init_image``: a base64 PNG (encoded by the model's VQGAN) or the picture's codes (a sequence of
+               top_p: float = 1.0, cond_scale: float = 1.0, init_image=None, mask=None, num_init_img_tokens=None,
+               seed: Optional[int] = None) -> Future:
+        """``seed``: image ``i`` of the request draws its noise from ``(seed, noise_row = i)``; the result carries it.
+        ``init_image``: a base64 PNG (encoded by the model's VQGAN) or the picture's codes (a sequence of
         image_seq_len integers; works without a VAE). ``mask``: a base64 PNG (white = regenerate, framed like the
         picture) or an array over the codes / pixels (``dalle_amd.models.dalle.code_mask``). Without a mask the first
         ``num_init_img_tokens`` codes (default 0.4375 of them) are kept. The picture applies to every image of the
@@ -103,8 +122,16 @@ class BatchingGenerator:
         if cond_scale < 0:
             raise ValueError("cond_scale must be >= 0")
         image, regen = self._picture(init_image, mask, num_init_img_tokens)
-        job = _Job(list(prompts), int(images_per_prompt), (float(temperature), int(top_k), float(top_p), float(cond_scale)),
-                   image, regen)
+        params = (float(temperature), int(top_k), float(top_p), float(cond_scale))
+        if seed is not None and not -(2 ** 63) <= int(seed) < 2 ** 63:
+            raise ValueError("seed must fit 64 bits")
+        if self.mix_params:  # one key per engine kind; a seed of the request's own if it brought none
+            job = _Job(list(prompts), int(images_per_prompt), ("mix", params[3] != 1.0), image, regen, params,
+                       secrets.randbits(62) if seed is None else int(seed))
+        elif seed is not None:  # seeded requests of the same parameters share a batch, apart from the unseeded ones
+            job = _Job(list(prompts), int(images_per_prompt), params + ("seeded",), image, regen, params, int(seed))
+        else:
+            job = _Job(list(prompts), int(images_per_prompt), params, image, regen)
         if not job.prompts or job.n < 1:
             raise ValueError("need at least one prompt and images_per_prompt >= 1")
         if job.images > self.max_batch:
@@ -231,13 +258,26 @@ class BatchingGenerator:
             padded *= 2
         padded = min(padded, self.max_batch) if n <= self.max_batch else n
         ids = self._ids(prompts + [prompts[-1]] * (padded - n)).to(self.device)
-        temperature, top_k, top_p, cond_scale = batch[0].key
-        guided = cond_scale != 1.0
-        cache = self.guided_engines if guided else self.engines
+        rows = batch[0].rows
+        if rows:
+            # one table row per picture: the job's parameters and seed, image i of the job on noise row i; the padded
+            # rows copy the last row, as they do for pictures and masks
+            per = [job.params + (job.seed, i) for job in batch for i in range(job.images)]
+            per += [per[-1]] * (padded - n)
+            temperature, top_k, top_p, cond_scale, seeds, noise = (list(c) for c in zip(*per))
+            guided = any(job.params[3] != 1.0 for job in batch)
+            cache = self.guided_row_engines if guided else self.row_engines
+        else:
+            temperature, top_k, top_p, cond_scale = batch[0].key
+            guided = cond_scale != 1.0
+            cache = self.guided_engines if guided else self.engines
         eng = cache.get(padded)
         if eng is None:
-            eng = cache[padded] = make_decode_engine(self.model, padded, device=self.device, **({"guided": True} if guided else {}))
+            eng = cache[padded] = make_decode_engine(self.model, padded, device=self.device, **({"guided": True} if guided else {}),
+                                                     **({"row_params": True} if rows else {}))
         kw = {"cond_scale": cond_scale} if guided else {}
+        if rows:
+            kw.update(seed=seeds, noise_row=noise)
         if any(job.image is not None for job in batch):
             # one mask per row: a row without a picture regenerates everything (the ordinary path); the padded rows
             # copy the last row's picture and mask
@@ -267,7 +307,7 @@ class BatchingGenerator:
             res = {"images": [_png_b64(a) for a in arr[off:off + k]] if arr is not None else [],
                    "codes": codes[off:off + k].cpu().tolist() if arr is None else None,
                    "batch_images": n, "batch_padded": padded, "generate_seconds": round(gpu_s, 4),
-                   "queue_seconds": round(t0 - job.t_submit, 4)}
+                   "queue_seconds": round(t0 - job.t_submit, 4), "seed": job.seed}
             off += k
             self.stats["requests"] += 1
             self.stats["images"] += k
@@ -279,13 +319,14 @@ class MultiDeviceGenerator:
     thread); ``submit`` routes each request to the device with the fewest images in flight, so a node's
     GPUs batch and decode independently. Same interface as a single generator."""
 
-    def __init__(self, model, tokenizer, devices: List[str], max_batch: int = 64, batch_window_ms: float = 20.0):
+    def __init__(self, model, tokenizer, devices: List[str], max_batch: int = 64, batch_window_ms: float = 20.0,
+                 mix_params: bool = False):
         if not devices:
             raise ValueError("need at least one device")
         self.gens: List[BatchingGenerator] = []
         for i, d in enumerate(devices):
             m = model if i == len(devices) - 1 else copy.deepcopy(model)  # the last device takes the original
-            self.gens.append(BatchingGenerator(m.to(d).eval(), tokenizer, d, max_batch, batch_window_ms))
+            self.gens.append(BatchingGenerator(m.to(d).eval(), tokenizer, d, max_batch, batch_window_ms, mix_params))
         self.max_batch = self.gens[0].max_batch
         self._inflight = [0] * len(self.gens)
         self._lock = threading.Lock()
@@ -302,6 +343,20 @@ class MultiDeviceGenerator:
         return out
 
     @property
+    def row_engines(self) -> Dict[int, DecodeEngine]:
+        out: Dict[int, DecodeEngine] = {}
+        for g in self.gens:
+            out.update(g.row_engines)
+        return out
+
+    @property
+    def guided_row_engines(self) -> Dict[int, DecodeEngine]:
+        out: Dict[int, DecodeEngine] = {}
+        for g in self.gens:
+            out.update(g.guided_row_engines)
+        return out
+
+    @property
     def stats(self) -> Dict[str, float]:
         tot = {"requests": 0, "images": 0, "batches": 0, "gpu_seconds": 0.0}
         for g in self.gens:
@@ -311,14 +366,15 @@ class MultiDeviceGenerator:
         return tot
 
     def submit(self, prompts: List[str], images_per_prompt: int = 1, temperature: float = 1.0, top_k: int = 0,
-               top_p: float = 1.0, cond_scale: float = 1.0, init_image=None, mask=None, num_init_img_tokens=None) -> Future:
+               top_p: float = 1.0, cond_scale: float = 1.0, init_image=None, mask=None, num_init_img_tokens=None,
+               seed: Optional[int] = None) -> Future:
         n = len(prompts) * int(images_per_prompt)
         with self._lock:
             i = min(range(len(self.gens)), key=lambda k: (self._inflight[k], k))
             self._inflight[i] += n
         try:
             fut = self.gens[i].submit(prompts, images_per_prompt, temperature, top_k, top_p, cond_scale, init_image, mask,
-                                      num_init_img_tokens)
+                                      num_init_img_tokens, seed)
         except Exception:
             with self._lock:
                 self._inflight[i] -= n
@@ -359,6 +415,7 @@ try:  # the HTTP layer is optional: BatchingGenerator works without fastapi / py
         init_image: Optional[str] = None  # base64 PNG: the picture to edit
         mask: Optional[str] = None  # base64 PNG, white = regenerate (needs init_image)
         num_init_img_tokens: Optional[int] = Field(None, ge=0)  # without a mask: how many leading codes to keep
+        seed: Optional[int] = Field(None, ge=-(2 ** 63), lt=2 ** 63)  # image i draws from (seed, noise row i); echoed back
 except ImportError:  # pragma: no cover
     GenerateRequest = None
 
@@ -384,7 +441,7 @@ def create_app(gen):
     def generate(req: GenerateRequest):
         try:
             fut = gen.submit(req.prompts, req.images_per_prompt, req.temperature, req.top_k, req.top_p, req.cond_scale,
-                             req.init_image, req.mask, req.num_init_img_tokens)
+                             req.init_image, req.mask, req.num_init_img_tokens, req.seed)
         except ValueError as e:
             raise HTTPException(status_code=400, detail=str(e))
         return fut.result()
@@ -402,6 +459,8 @@ def main(argv=None):
     ap.add_argument("--max-batch", type=int, default=64)
     ap.add_argument("--devices", default="auto", help='"all" GPUs of the node, a list like "0,1,2,3", or "auto" (one)')
     ap.add_argument("--batch-window-ms", type=float, default=20.0)
+    ap.add_argument("--mix-params", action="store_true",
+                    help="batch requests with different sampling parameters together, on row-parameter engines")
     ap.add_argument("--host", default="127.0.0.1")
     ap.add_argument("--port", type=int, default=8000)
     args = ap.parse_args(argv)
@@ -417,9 +476,10 @@ def main(argv=None):
     wrapper.model.vae = VQGanVAE(args.vqgan, args.vqgan_config).eval()
     if len(devices) == 1:
         gen = BatchingGenerator(wrapper.model.to(devices[0]).eval(), tokenizer, devices[0], args.max_batch,
-                                args.batch_window_ms)
+                                args.batch_window_ms, args.mix_params)
     else:
-        gen = MultiDeviceGenerator(wrapper.model.eval(), tokenizer, devices, args.max_batch, args.batch_window_ms)
+        gen = MultiDeviceGenerator(wrapper.model.eval(), tokenizer, devices, args.max_batch, args.batch_window_ms,
+                                   args.mix_params)
     logger.info(f"serving on {gen.device}")
     import uvicorn
 
