@@ -368,10 +368,13 @@ __device__ __forceinline__ void dq_tile(f32x16& dq0, f32x16& dq1, const __bf16* 
 // phases as the forward: (A) the text key tiles, staged cooperatively two per barrier step with the
 // next pair's loads in flight; (B) each image query block streams ITS OWN local key tiles through a
 // private LDS slot (no workgroup barrier, no wave idling on the other blocks' tiles).
-// FUSE_LOCAL (axial row / col, rotary-fused output only): an image key tile is attended by exactly one
-// query tile -- its own row's (column's) -- so that tile's dK / dV are produced right here, by the wave
+// FUSE_LOCAL (axial row / col with S <= 32, rotary-fused output only): a row (column) fits in one 32-key tile,
+// so an image key tile is attended by exactly one query tile -- itself -- and its dK / dV are produced right here
+// from the diagonal tile alone (query_mask(g, ks, qb)), by the wave
 // that owns the query tile, from the K / V it already staged and the Q / dO it already holds: the
 // separate image-key dK/dV kernel (a launch that re-read Q, dO, K and V of every local tile) disappears.
+// At S = 64 a row spans two tiles and the first half-row's keys are also attended by the second half-row's
+// query tile: the launcher keeps the separate kernel there.
 // Text tiles are register-staged, two per barrier step (LDS-DMA staging two or three tiles per step, one or two
 // steps ahead, measured no different: profiles/r6_attn_staging_depth.txt).
 template <int MINB, bool FUSE_LOCAL, bool PREFETCH_LOCAL = false>
@@ -970,9 +973,9 @@ void attn_bwd(const void* q, const void* k, const void* v, const void* out, cons
     return;
   }
   dim3 grid((g.Np / 32 + 3) / 4, BH);
-  // axial row / col: every image key tile is attended by exactly its own query tile -> dK / dV of the
-  // image keys inside the dQ kernel (rotary-fused output path)
-  const bool fuse_local = dqkv != nullptr && (g.pattern == 1 || g.pattern == 2);
+  // axial row / col, a row (column) within one 32-key tile (S <= 32): every image key tile is attended by
+  // exactly its own query tile -> dK / dV of the image keys inside the dQ kernel (rotary-fused output path)
+  const bool fuse_local = dqkv != nullptr && (g.pattern == 1 || g.pattern == 2) && g.S <= 32;
   const int ntext = g.Tp / 32, nimg = g.Np / 32 - ntext;
   if (fuse_local)
     hipLaunchKernelGGL((attn_bwd_dq_kernel<3, true, false>), grid, dim3(256), 0, st, (const __bf16*)q, (const __bf16*)k,

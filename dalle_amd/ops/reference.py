@@ -65,13 +65,14 @@ def qkv_rotary(qkv: torch.Tensor, heads: int, cos: torch.Tensor, sin: torch.Tens
 
 
 def sparse_attention_core(q, k, v, geom: AttnGeometry, attn_type: str):
-    """q (pre-scaled), k, v: (B, H, n, D) -> (B, n, H*D); dense masked softmax in fp32."""
+    """q (pre-scaled), k, v: (B, H, n, D) -> (B, n, H*D); dense masked softmax in fp32 (float64 inputs: in float64)."""
     B, H, n, D = q.shape
     mask = static_mask(geom, attn_type, n, device=q.device)
-    scores = torch.matmul(q.float(), k.float().transpose(-1, -2))
+    acc = torch.float64 if q.dtype == torch.float64 else torch.float32
+    scores = torch.matmul(q.to(acc), k.to(acc).transpose(-1, -2))
     scores = scores.masked_fill(~mask, -torch.finfo(torch.float32).max)
     p = torch.softmax(scores, dim=-1)
-    out = torch.matmul(p, v.float()).to(q.dtype)
+    out = torch.matmul(p, v.to(acc)).to(q.dtype)
     return out.transpose(1, 2).reshape(B, n, H * D)
 
 

@@ -1,4 +1,7 @@
-"""Numerics of every HIP kernel against a plain PyTorch fp32 reference of the same op (MI355X only)."""
+"""Numerics of the HIP kernels against a plain PyTorch fp32 reference of the same op, whole-tensor relative L2 norms
+(MI355X only). The sparse attention and rotary kernels are also checked one by one, per element against float64 with
+derived bounds and planted mask edges, in ``test_attention_kernels_gpu.py``; the VQGAN kernels in
+``test_vqgan_kernels_gpu.py`` and ``test_vqgan_encoder_kernels_gpu.py``."""
 import pytest
 import torch
 import torch.nn.functional as F
