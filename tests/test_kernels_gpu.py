@@ -481,9 +481,11 @@ def test_transpose_cast_bf16_bitwise(cuda, shape):
 
 @pytest.mark.parametrize("V", [8192, 32356, 1064, 516, 1000])
 def test_xent_colsum(cuda, V):
-    """Fused CE + in-place dlogits + bias-gradient column sums (register-resident forms up to 32768 columns,
-    the LDS-accumulator form beyond) against fp32 PyTorch; the column sums are of the bf16 dlogits the GEMMs
-    consume."""
+    """Fused CE + in-place dlogits + bias-gradient column sums against fp32 PyTorch; the column sums are of the bf16
+    dlogits the GEMMs consume. Every V here is a multiple of 4 and at most 32768, so only the two register-resident
+    forms run (8192, 1064, 1000: the 4-wave form; 32356, 516: the 16-wave form), their grid stride included
+    (R = 2000 rows over 1024 / 512 workgroups). The LDS-accumulator form (a width that is no multiple of 4, or in
+    (32768, 35000]) is run by ``test_train_kernels_gpu.py::test_xent``."""
     from dalle_amd.ops import hip_ops
 
     C = hip_ops.C()
